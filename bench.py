@@ -18,15 +18,23 @@ every component's nodes (north_star's layout: RCCL allgather of the candidate li
 min-allreduce of the bounds per round, host-driven rounds).  Either way a strong step is bounded
 by the longest component's serial commit chain, so strong scaling is flat (DESIGN.md §3.5 gives
 the predicted curves); a strong N > 1 run also reports the weak rate as the extra key
-`weak_scaling` (--no-weak-extra skips it).
+`weak_scaling` (--full; --no-weak-extra skips it).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c3o|c2|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c3o|c2|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps once and prints the line (`value`, `ms_per_step`, and
+the roofline of the timed steps from the engine's own HIP events); --dump-outputs DIR also writes
+what the last timed step returned as DIR/<name>.npy (the generator is seeded, so two builds can be
+compared output for output).  --full adds every leg that takes runs of its own: the median of 3
+timed runs, `kernel_path_value`, the live PMC passes behind `roofline.traffic`, `cpu_baseline`,
+the node-sharding price and the N > 1 weak leg.
 
 Rank 0 prints ONE JSON line.  `roofline` is live: per-launch kernel time from the engine's HIP
 events (on the engine's stream), algorithmic work from DESIGN.md §5; `traffic` comes from the
-committed PMC profile named in `traffic_source`.  `cpu_baseline` times the CPU restatements
-(oracle/: naive port, component-aware, multicore) on bounded samples of the same workload.
+PMC passes (--full) or the committed PMC profile, as `traffic_source` says.  `cpu_baseline`
+(--full) times the CPU restatements (oracle/: naive port, component-aware, multicore) on bounded
+samples of the same workload.
 """
 from __future__ import annotations
 
@@ -121,8 +129,16 @@ def parse_args():
                          "admission latency (10 concurrent callers against the c3 node table); c2a / c3a / "
                          "c5a: the same clusters with an array-expanded pending queue (runs of identical "
                          "pods, synth.expand_arrays) — not a BASELINE config")
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed runs of --steps steps each; value = their median (BASELINE.md:26)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the median of 3 timed runs, the HBM-resident "
+                         "rate, the live PMC passes, the CPU baselines, the node-sharding price and (N>1 strong) "
+                         "the weak leg; the --no-* switches below take single legs out of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (placements, start "
+                         "slots, job counts) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed runs of --steps steps each; value = their median (BASELINE.md:26); "
+                         "default 1, or 3 with --full")
     ap.add_argument("--no-shard-price", action="store_true",
                     help="skip the one-GPU price of north_star's node-sharded layout (c3 / c3o)")
     ap.add_argument("--admit-pods", type=int, default=300, help="admit: pods per caller thread")
@@ -160,6 +176,10 @@ def _pinned(keep, a):
 
 def main():
     a = parse_args()
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    if not a.full:  # a plain run times its steps and nothing else
+        a.no_device_path = a.no_live_pmc = a.no_cpu = a.no_shard_price = a.no_weak_extra = True
     if a.workload == "admit":
         import torch
         torch.cuda.set_device(0)
@@ -234,15 +254,16 @@ def main():
 
     # ---- HBM-resident path (kernel_path_value) --------------------------------------------------
     dev = torch.device("cuda", local)
-    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
-    d_nodes = [T(nodes.cpu_free), T(nodes.mem_free), T(nodes.gpu_free), T(nodes.avail_min),
-               T(nodes.part_mask.view(np.int32))]
-    d_jobs = [T(jobs.cpu), T(jobs.mem), T(jobs.gpu), T(jobs.wall), T(jobs.part.view(np.int16)),
-              T(jobs.nodes_k.view(np.int16))]
-    d_out = torch.empty(jobs.j * kmax, dtype=torch.int32, device=dev)
-    if tl:
-        d_rel = [T(x) for x in (tline.off, tline.slot, tline.cpu, tline.mem, tline.gpu)]
-        d_start = torch.empty(jobs.j, dtype=torch.int32, device=dev)
+    if not a.no_device_path:
+        T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        d_nodes = [T(nodes.cpu_free), T(nodes.mem_free), T(nodes.gpu_free), T(nodes.avail_min),
+                   T(nodes.part_mask.view(np.int32))]
+        d_jobs = [T(jobs.cpu), T(jobs.mem), T(jobs.gpu), T(jobs.wall), T(jobs.part.view(np.int16)),
+                  T(jobs.nodes_k.view(np.int16))]
+        d_out = torch.empty(jobs.j * kmax, dtype=torch.int32, device=dev)
+        if tl:
+            d_rel = [T(x) for x in (tline.off, tline.slot, tline.cpu, tline.mem, tline.gpu)]
+            d_start = torch.empty(jobs.j, dtype=torch.int32, device=dev)
 
     def step_dev():
         eng.load_nodes_device(*d_nodes)
@@ -285,6 +306,10 @@ def main():
     el, stats_host, runs_host = timed(step_host)
     s0 = stats_host[-1]
     assert s0["placed"] + s0["unplaced"] + s0["rejected"] == jobs.j  # output sanity every run
+    if a.dump_outputs:  # before any other leg reuses the host buffers
+        dump_outputs(a.dump_outputs, rank, placements=h_out.reshape(jobs.j, kmax),
+                     start=h_start if tl else None,
+                     counts=np.array([s0["placed"], s0["unplaced"], s0["rejected"]], np.float64))
     mult = world if weak else 1
     value = jobs.j * a.steps / el * mult
     el_dev, stats, runs_dev = (None, stats_host, None) if a.no_device_path else timed(step_dev)
@@ -392,6 +417,27 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def dump_outputs(out_dir, rank, **arrays):
+    """What the last timed step handed its caller, one float32 .npy per array (node indices, slots
+    and job counts are far below 2^24, so float32 holds them exactly; counts stay float64).  An
+    array over its share of DUMP_BUDGET is cut to a fixed, seeded sample of its entries.  Ranks
+    beyond the first (N > 1) add .rank<r> to the name."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_BUDGET // len(arrays)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if arr.dtype != np.float64:
+            arr = arr.astype(np.float32)
+        if arr.nbytes > share:
+            pick = np.sort(np.random.default_rng(0).choice(arr.size, share // arr.itemsize, replace=False))
+            arr = arr.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
 
 
 def live_traffic(workload, kernel, timeout=240):

@@ -1,6 +1,7 @@
 """bench.py keeps the driver's contract: one JSON line with the required keys, the roofline and
-CPU-baseline objects, for the C3 headline, the C5 and c3o workloads; N>1 rehearsed with two ranks on
-one GPU (gloo for the timing collectives; the strong split exchanges through the host)."""
+(--full) CPU-baseline objects, for the C3 headline, the C5 and c3o workloads; a plain run times its
+steps only and --dump-outputs writes what they computed; N>1 rehearsed with two ranks on one GPU
+(gloo for the timing collectives; the strong split exchanges through the host)."""
 import json
 import os
 import socket
@@ -31,7 +32,7 @@ BACKFILL = {"naive-port", "component-aware", "run-length", "multicore"}
 @pytest.mark.parametrize("workload", ["c3", "c5", "c3o"])
 def test_bench_line(workload):
     d = run(["bench.py", "--workload", workload, "--steps", "1", "--warmup", "1", "--cpu-scale", "0.01",
-             "--no-live-pmc"])
+             "--no-live-pmc", "--full"])
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["value"] > 0 and d["kernel_path_value"] > 0
     assert set(d["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
     cb = d["cpu_baseline"]
@@ -44,10 +45,32 @@ def test_bench_line(workload):
         assert d["node_sharding_1gpu"]["ms_per_step"] > 0
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run: exactly --steps timed steps in one timed run, none of the --full legs, and
+    --dump-outputs holds the last step's placements and job counts (checked against the oracle)."""
+    import numpy as np
+
+    from fitgpu import synth
+    from oracle import pyoracle as po
+    d = run(["bench.py", "--workload", "c2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert KEYS <= set(d) and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["timing"]["repeats"] == 1 and d["timing"]["value_runs"] == [d["value"]]
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / d["config"]["jobs"] - 1) < 1e-3  # one step = all jobs
+    assert d["cpu_baseline"] is None and d["kernel_path_value"] is None and "node_sharding_1gpu" not in d
+    assert not (d["roofline"]["traffic_source"] or "").startswith("live")
+    nodes, jobs, parts = synth.make_config("c2")
+    ref, rst, _ = po.ref_place(nodes, jobs, parts)
+    assert sorted(os.listdir(tmp_path)) == ["counts.npy", "placements.npy"]
+    out = np.load(tmp_path / "placements.npy")
+    assert out.dtype == np.float32 and np.array_equal(out, ref.reshape(jobs.j, 1).astype(np.float32))
+    counts = np.load(tmp_path / "counts.npy")
+    assert counts.dtype == np.float64 and counts.tolist() == [rst["placed"], rst["unplaced"], rst["rejected"]]
+
+
 def test_bench_live_traffic():
     """roofline.traffic measured in the run: two rocprofv3 --pmc passes over a child bench run."""
     d = run(["bench.py", "--workload", "c2", "--steps", "2", "--warmup", "1", "--no-cpu", "--repeats", "1",
-             "--no-shard-price"], timeout=600)
+             "--no-shard-price", "--full"], timeout=600)
     assert d["roofline"]["traffic"] > 0 and d["roofline"]["traffic_source"].startswith("live")
 
 
@@ -79,7 +102,7 @@ def test_bench_two_rank_strong_rehearsal(shard_mode, workload):
     d = run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
              "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--rehearse",
              "--scaling", "strong", "--shard-mode", shard_mode, "--workload", workload, "--no-device-path",
-             "--repeats", "1"])
+             "--repeats", "1", "--full"])
     jobs = 1_000_000 if workload == "c3" else 65_536
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["jobs"] == jobs
     assert ("component" in d["config"]["parallelism"]) == (shard_mode == "auto")

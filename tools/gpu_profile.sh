@@ -17,8 +17,10 @@ for ctr in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BU
   timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d gpurun_out/${TAG}_pmc$i -o pmc -- python3 bench.py --steps 2 --warmup 1 $P > gpurun_out/${TAG}_pmc$i.out 2>&1 || { echo "c3 pmc pass $i failed"; exit 1; }
   timeout -s KILL 150 rocprofv3 --pmc $ctr --output-format csv -d gpurun_out/${TAG}_pmc_c5_$i -o pmc -- python3 bench.py --workload c5 --steps 1 --warmup 1 $P > gpurun_out/${TAG}_pmc_c5_$i.out 2>&1 || { echo "c5 pmc pass $i failed"; exit 1; }
 done
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 for w in c2 c3o c4; do
-  timeout -k 10 400 python -u bench.py --workload $w > gpurun_out/${TAG}_${w}_bench.json 2> gpurun_out/${TAG}_${w}_bench.err || { tail -20 gpurun_out/${TAG}_${w}_bench.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --workload $w --full > $OUT/${TAG}_${w}_bench.json 2> $OUT/${TAG}_${w}_bench.err || { tail -20 $OUT/${TAG}_${w}_bench.err; exit 1; }
 done
 timeout -k 10 300 python -u bench.py --workload admit > gpurun_out/${TAG}_admit_bench.json 2> gpurun_out/${TAG}_admit_bench.err || { tail -20 gpurun_out/${TAG}_admit_bench.err; exit 1; }
 cat gpurun_out/${TAG}_admit_bench.json
