@@ -169,6 +169,69 @@ int fit_read_nodes(fit_ctx* ctx, int32_t* cpu_free, int32_t* mem_free, int32_t* 
  * replacement for the allocation-blind sum of GetPartitionCapacity (node.go:183-190). */
 int fit_partition_free(fit_ctx* ctx, int32_t p, int64_t* cpu, int64_t* mem_mib, int64_t* gpu);
 
+/* ---- why a job does not fit ----------------------------------------------
+ * The half of kube-scheduler's answer that fit_place does not give: its FailedScheduling event
+ * ("0/5 nodes are available: 3 Insufficient cpu, 2 Insufficient memory").  fit_explain judges each
+ * of J jobs ALONE against the context's current node table — the rows fit_read_nodes returns, with
+ * the loaded avail_min / part_mask — and changes nothing: no job consumes anything, the order of
+ * the jobs does not matter.  One 32-byte row per job. */
+#define FIT_WHY_FITS 0        /* fit >= need: a fit_place of this job alone would place it now  */
+#define FIT_WHY_PARTITION 1   /* part >= P (the partitions of fit_load_partitions)              */
+#define FIT_WHY_LIMIT_TIME 2  /* wall > the partition's MaxTime                                  */
+#define FIT_WHY_LIMIT_CPUS 3  /* cpu  > the partition's MaxCPUsPerNode                           */
+#define FIT_WHY_LIMIT_MEM 4   /* mem  > the partition's MaxMemPerNode                            */
+#define FIT_WHY_NO_NODES 5    /* members == 0                                                    */
+#define FIT_WHY_RESOURCES 6   /* fit < need                                                      */
+/* Precedence: the order above from FIT_WHY_PARTITION on (first match wins; the limits in
+ * fit_place's order: time, cpus, mem), FIT_WHY_FITS last.  Codes 1-4 are exactly the jobs fit_place
+ * marks FIT_REJECTED; their counters are all 0 (need is still set). */
+typedef struct {
+    int32_t code;        /* FIT_WHY_*                                                        */
+    int32_t need;        /* nodes_k, 0 treated as 1                                          */
+    int32_t members;     /* nodes with the job's partition bit set (a node whose State took  */
+                         /* it out of every partition is in none)                            */
+    int32_t fit;         /* members that pass all four feasibility terms now                 */
+    int32_t short_cpu;   /* members with cpu_free  < cpu   — counts overlap, as kube-        */
+    int32_t short_mem;   /* members with mem_free  < mem     scheduler's do: a node short of */
+    int32_t short_gpu;   /* members with gpu_free  < gpu     two things is counted twice     */
+    int32_t short_time;  /* members with avail_min < wall                                    */
+} fit_why;
+/* Host pointers; nodes_k may be NULL (= all 1).  j == 0 returns 0 whatever the pointers are.
+ * FIT_E_INVAL: NULL ctx / arrays, a negative demand or nodes_k > FIT_MAX_K (the whole call fails,
+ * as fit_place's does).  FIT_E_STATE: before fit_load_nodes; while a timeline is loaded (the
+ * backfill view is fit_place_tl's start slot); on a context created with world > 1 or
+ * FIT_FLAG_COLLECTIVES (a rank holds no whole answer).  Three bounded launches, no persistent
+ * grid: the call neither takes the per-GPU persistent-launch lock nor needs the watchdog. */
+int fit_explain(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, fit_why* out);
+/* Same with device pointers (inputs resident in HBM, the rows written in HBM). */
+int fit_explain_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem,
+                       const int32_t* gpu, const int32_t* wall, const uint16_t* part,
+                       const uint16_t* nodes_k, fit_why* out);
+/* Diagnostic, for measurement only (tools/explain_bench.py): device time of the last successful
+ * fit_explain_device on this context, in milliseconds — HIP events on the context's own stream
+ * around its launches, which a caller cannot record from outside.  FIT_E_STATE when there has
+ * been none. */
+int fit_explain_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text in kube-scheduler's shape, NUL-terminated into buf.  Host only: no
+ * device, no context.  Returns the length written (without the NUL), or FIT_E_INVAL: NULL
+ * arguments, an unknown code, or a buffer too small for the text and its NUL (256 bytes always
+ * suffice).  The exact texts, <x> a decimal field of the row:
+ *   FIT_WHY_FITS        "<fit>/<members> nodes fit now"
+ *   FIT_WHY_RESOURCES   "<fit>/<members> nodes fit now: <short_cpu> insufficient cpu,
+ *                        <short_mem> insufficient memory, <short_gpu> insufficient gpu,
+ *                        <short_time> not available for the walltime"
+ *                       — on one line, terms joined by ", "; a term whose count is 0 is left out,
+ *                       and with no term left the ": " goes too
+ *     both with " (need <need>)" after "now" when need > 1, e.g.
+ *     "0/6273 nodes fit now (need 2): 5120 insufficient cpu, 73 insufficient memory"
+ *   FIT_WHY_NO_NODES    "no schedulable node in the partition"
+ *   FIT_WHY_LIMIT_TIME  "walltime exceeds the partition's MaxTime"
+ *   FIT_WHY_LIMIT_CPUS  "cpus per node exceed the partition's MaxCPUsPerNode"
+ *   FIT_WHY_LIMIT_MEM   "memory per node exceeds the partition's MaxMemPerNode"
+ *   FIT_WHY_PARTITION   "unknown partition" */
+int fit_why_message(const fit_why* w, char* buf, int32_t buflen);
+
 /* ---- time-windowed backfill (BASELINE config C5) -------------------------
  * Each node's free resources over a horizon of `slots` slots of `slot_min` minutes (slots <=
  * 1024): the node table of the last fit_load_nodes is the state at slot 0, and the jobs already
@@ -392,6 +455,13 @@ int fit_admitter_partition_free(fit_admitter* a, int32_t p, int64_t* cpu, int64_
 int fit_admitter_confirm(fit_admitter* a, int64_t ticket);
 int fit_admitter_release(fit_admitter* a, int64_t ticket);
 int fit_admitter_set_ttl(fit_admitter* a, int32_t loads);
+/* fit_explain of n requests against the admitter's table as the next batch would see it: the
+ * engine's copy is first brought up to date the way a batch does it, so open reservations count
+ * (a node whose last GPU is reserved shows in short_gpu) and a released one no longer does.
+ * Thread-safe; it takes the lock that placements and loads take and does not queue behind the
+ * coalescer, so it waits for at most the batch being placed.  priority and flags are ignored.
+ * n == 0 returns 0.  Errors as fit_explain. */
+int fit_admitter_explain(fit_admitter* a, const fit_admit_req* reqs, int32_t n, fit_why* out);
 /* Open reservations / requests queued for the next batch (monitoring, tests). */
 int fit_admitter_reservations(fit_admitter* a);
 int fit_admitter_pending(fit_admitter* a);

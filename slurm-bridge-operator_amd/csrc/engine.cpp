@@ -362,6 +362,12 @@ struct fit_ctx {
     HBuf<int32_t> h_small;
     DBuf<uint8_t> jpack;    // fit_place's job columns of a small batch, packed: one H2D copy
     HBuf<uint8_t> h_jpack;
+    // fit_explain: the rows on the device (host entry point; the flag word rides behind them), the
+    // flag word of the device entry point, and the pinned copy both come back into
+    DBuf<fit_why> ex_out;
+    DBuf<int32_t> ex_bad;
+    HBuf<fit_why> h_ex;
+    double ex_ms = -1;      // device time of the last fit_explain_device (fit_explain_ms)
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -461,6 +467,9 @@ struct fit_ctx {
         h_small.release();
         jpack.release();
         h_jpack.release();
+        ex_out.release();
+        ex_bad.release();
+        h_ex.release();
         h_x.release();
         xcount.release();
         h_count.release();
@@ -1467,6 +1476,58 @@ int place_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem,
     return 0;
 }
 
+// ------------------------------------------------------------------------ fit_explain
+// classify, (a long queue: the jobs in component order, launch_joblists),
+// count, finalise — a fixed sequence of bounded launches on the context's stream, no host loop and
+// no synchronisation in between; nothing here waits on another workgroup, so neither the watchdog
+// nor the persistent-launch lock is involved.  Device pointers; *bad and the rows are valid once
+// the caller has drained the stream.
+static_assert(EX_FITS == FIT_WHY_FITS && EX_PARTITION == FIT_WHY_PARTITION && EX_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
+                  EX_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && EX_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
+                  EX_NO_NODES == FIT_WHY_NO_NODES && EX_RESOURCES == FIT_WHY_RESOURCES && FIT_KMAX == FIT_MAX_K,
+              "fit_device.h and fitgpu.h disagree");
+static_assert(sizeof(fit_why) == 32, "fit_why is 32 bytes");
+// below this many jobs the caller's order is kept: the sort's three launches cost more than the
+// component passes a mixed wave adds
+constexpr int32_t kExplainSortJobs = 256;
+
+int explain_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                 const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out, int32_t* bad) {
+    const int C = c->ncomp;
+    hipStream_t st = c->st;
+    if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    HIP_TRY(launch_explain_classify(st, c->d_ptab.p, c->np, cpu, mem, gpu, wall, part, nk, J, out, c->jcomp.p, bad));
+    const int32_t *jl = nullptr, *live = nullptr;
+    if (J > kExplainSortJobs && C > 1) {
+        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
+            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
+            return FIT_E_OOM;
+        int32_t* g = c->jls.p + joblists_scratch_ints(J);
+        int32_t* jbd = g + 2;
+        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
+        jl = c->jl.p;
+        live = jbd + C;  // jobs that have a component
+    }
+    ExplainComps ec;
+    ec.ncomp = C;
+    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+    HIP_TRY(launch_explain(st, c->rec.p, ec, cpu, mem, gpu, wall, part, J, c->jcomp.p, jl, live,
+                           explain_slices(J, c->cls_maxn, c->cus), out));
+    return 0;
+}
+
+int check_explain_args(fit_ctx* c, int32_t j, const void* a, const void* b, const void* d, const void* e,
+                       const void* f, const void* out) {
+    if (!c) return fail(FIT_E_INVAL, "null ctx");
+    if (j < 0) return fail(FIT_E_INVAL, "j=%d", j);
+    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
+    if (c->collective()) return fail(FIT_E_STATE, "fit_explain on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
+    if (c->have_tl) return fail(FIT_E_STATE, "fit_explain while a timeline is loaded");
+    if (j > 0 && (!a || !b || !d || !e || !f || !out)) return fail(FIT_E_INVAL, "bad job arrays");
+    return 0;
+}
+
 int load_timeline_impl(fit_ctx* c, int32_t slots, int32_t slot_min, int64_t ne) {
     if (c->tlhdr.ensure(std::max(c->nn, 1)) ||
         c->slab.ensure((size_t)std::max(c->nn, 1) * TL_MAX_SLOTS) || c->tl_err.ensure(1) ||
@@ -1806,6 +1867,66 @@ int fit_place_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* m
     rc = place_impl(c, j, cpu, mem, gpu, wall, part, nk, kmax, out, stats);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+int fit_explain(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out) {
+    int rc = check_explain_args(c, j, cpu, mem, gpu, wall, part, out);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the columns packed in pinned memory, ONE copy to the device (as fit_place's small batches)
+    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j, bh4 = (bh + 3) & ~(size_t)3;
+    const size_t tot = 4 * b + 2 * bh4;
+    if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot) || c->ex_out.ensure((size_t)j + 1) ||
+        c->h_ex.ensure((size_t)j + 1))
+        return FIT_E_OOM;
+    uint8_t* h = c->h_jpack.p;
+    memcpy(h, cpu, b);
+    memcpy(h + b, mem, b);
+    memcpy(h + 2 * b, gpu, b);
+    memcpy(h + 3 * b, wall, b);
+    memcpy(h + 4 * b, part, bh);
+    if (nk) memcpy(h + 4 * b + bh4, nk, bh);
+    HIP_TRY(hipMemcpyAsync(c->jpack.p, h, nk ? tot : 4 * b + bh4, hipMemcpyHostToDevice, c->st));
+    const uint8_t* d = c->jpack.p;
+    // the flag word behind the rows: rows and flag come back in ONE copy
+    int32_t* bad = reinterpret_cast<int32_t*>(c->ex_out.p + j);
+    rc = explain_impl(c, j, (const int32_t*)d, (const int32_t*)(d + b), (const int32_t*)(d + 2 * b),
+                      (const int32_t*)(d + 3 * b), (const uint16_t*)(d + 4 * b),
+                      nk ? (const uint16_t*)(d + 4 * b + bh4) : nullptr, c->ex_out.p, bad);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_ex.p, c->ex_out.p, sizeof(fit_why) * ((size_t)j + 1), hipMemcpyDeviceToHost,
+                           c->st));
+    HIP_TRY(j <= SMALL_ARGJ ? sync_small(c) : hipStreamSynchronize(c->st));
+    if (c->h_ex.p[j].code) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K);
+    memcpy(out, c->h_ex.p, sizeof(fit_why) * j);
+    return 0;
+}
+
+int fit_explain_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out) {
+    int rc = check_explain_args(c, j, cpu, mem, gpu, wall, part, out);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->ex_bad.ensure(1) || c->h_ex.ensure(1)) return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], c->st));
+    rc = explain_impl(c, j, cpu, mem, gpu, wall, part, nk, out, c->ex_bad.p);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], c->st));
+    HIP_TRY(hipMemcpyAsync(c->h_ex.p, c->ex_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->h_ex.p[0].code) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->ex_ms = ms;
+    return 0;
+}
+
+int fit_explain_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->ex_ms < 0) return fail(FIT_E_STATE, "no fit_explain_device yet");
+    *ms = c->ex_ms;
     return 0;
 }
 

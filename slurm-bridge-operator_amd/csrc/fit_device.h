@@ -1,5 +1,6 @@
 // fit_device.h — data layouts shared by the HIP kernels and the host engine.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 namespace fitgpu {
@@ -153,6 +154,32 @@ struct SmallBatch {
     int32_t cpu[SMALL_ARGJ], mem[SMALL_ARGJ], gpu[SMALL_ARGJ], wall[SMALL_ARGJ];
     uint16_t part[SMALL_ARGJ], nk[SMALL_ARGJ];
 };
+
+// ---- fit_explain (fit_explain.hip) ------------------------------------
+// The codes of include/fitgpu.h FIT_WHY_* (engine.cpp asserts they agree).
+enum ExplainCode : int32_t {
+    EX_FITS = 0,
+    EX_PARTITION = 1,
+    EX_LIMIT_TIME = 2,
+    EX_LIMIT_CPUS = 3,
+    EX_LIMIT_MEM = 4,
+    EX_NO_NODES = 5,
+    EX_RESOURCES = 6,
+};
+// Component node offsets in k_explain_count's kernel arguments: nb[c] .. nb[c + 1], c < ncomp.
+struct ExplainComps {
+    int32_t nb[33];
+    int32_t ncomp;
+};
+hipError_t launch_explain_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                   const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                   const uint16_t* jpart, const uint16_t* jk, int32_t nj, void* out, int8_t* jcomp,
+                                   int32_t* bad);
+hipError_t launch_explain(hipStream_t st, const NodeRec* rec, const ExplainComps& C, const int32_t* jcpu,
+                          const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                          int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
+                          void* out);
+int explain_slices(int32_t nj, int32_t maxn, int cus);
 
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {

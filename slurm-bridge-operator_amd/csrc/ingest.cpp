@@ -903,4 +903,42 @@ int fit_release_events(int32_t n, int32_t m, const int32_t* job_off, const int32
     return e;
 }
 
+// A fit_why row as one line in kube-scheduler's FailedScheduling shape; the texts are fixed in
+// include/fitgpu.h.  No device, no context.
+int fit_why_message(const fit_why* w, char* buf, int32_t buflen) {
+    if (!w || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    switch (w->code) {
+        case FIT_WHY_PARTITION: s = "unknown partition"; break;
+        case FIT_WHY_LIMIT_TIME: s = "walltime exceeds the partition's MaxTime"; break;
+        case FIT_WHY_LIMIT_CPUS: s = "cpus per node exceed the partition's MaxCPUsPerNode"; break;
+        case FIT_WHY_LIMIT_MEM: s = "memory per node exceeds the partition's MaxMemPerNode"; break;
+        case FIT_WHY_NO_NODES: s = "no schedulable node in the partition"; break;
+        case FIT_WHY_FITS:
+        case FIT_WHY_RESOURCES: {
+            s = std::to_string(w->fit) + "/" + std::to_string(w->members) + " nodes fit now";
+            if (w->need > 1) s += " (need " + std::to_string(w->need) + ")";
+            if (w->code == FIT_WHY_FITS) break;
+            const struct {
+                int32_t n;
+                const char* what;
+            } terms[] = {{w->short_cpu, "insufficient cpu"},
+                         {w->short_mem, "insufficient memory"},
+                         {w->short_gpu, "insufficient gpu"},
+                         {w->short_time, "not available for the walltime"}};
+            const char* sep = ": ";
+            for (const auto& t : terms) {
+                if (t.n == 0) continue;
+                s += sep + std::to_string(t.n) + " " + t.what;
+                sep = ", ";
+            }
+            break;
+        }
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 }  // extern "C"

@@ -30,7 +30,9 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_SHARD_AUTO,
                    FIT_SHARD_COMPONENTS, FIT_SHARD_NODES, FIT_TABLE_PIN, FIT_TABLE_STATE, FIT_UNPLACED, FIT_XCHG_ALLGATHER_U64,
                    FIT_XCHG_MAX_I32, FIT_XCHG_MIN_I32, FIT_XCHG_MIN_U64, XCHG_FN, FitAdmitReq, FitAdmitRes, FitError,
-                   FitJobResources, FitNode, FitNodeTable, FitOpts, FitPodLabels, FitResources, FitStats, check, lib)
+                   FitJobResources, FitNode, FitNodeTable, FitOpts, FitPodLabels, FitResources, FitStats, check, lib,
+                   FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
+                   FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -40,7 +42,8 @@ __all__ = [
     "FIT_SHARD_AUTO", "FIT_SHARD_NODES", "FIT_SHARD_COMPONENTS", "expand_hostlist", "ingest_nodes",
     "FIT_FLAG_COLLECTIVES", "Admitter", "array_tasks", "pod_demand", "script_with_nodelist",
     "partition_limits", "node_columns", "POD_LABEL_KEYS", "node_names", "set_max_array_size", "FIT_TABLE_STATE",
-    "FIT_TABLE_PIN",
+    "FIT_TABLE_PIN", "why_message", "WHY_DTYPE", "FIT_WHY_FITS", "FIT_WHY_PARTITION", "FIT_WHY_LIMIT_TIME",
+    "FIT_WHY_LIMIT_CPUS", "FIT_WHY_LIMIT_MEM", "FIT_WHY_NO_NODES", "FIT_WHY_RESOURCES",
 ]
 
 
@@ -328,6 +331,21 @@ def node_columns(nodes: list[Node], part_mask: int = 1):
     return Nodes(*(c[:n].copy() for c in cols))
 
 
+# ------------------------------------------------------------------------------- explain
+# one fit_why row (include/fitgpu.h), 32 bytes: what Engine.explain / Admitter.explain return
+WHY_DTYPE = np.dtype([(n, np.int32) for n, _ in FitWhy._fields_])
+
+
+def why_message(row) -> str:
+    """A fit_why row (an element of an explain() result, or any mapping / object with its fields)
+    as one line in kube-scheduler's shape (fit_why_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    w = FitWhy(*(int(get(n)) for n, _ in FitWhy._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_why_message(C.byref(w), buf, len(buf)), "fit_why_message")
+    return buf.raw[:n].decode()
+
+
 # ------------------------------------------------------------------------------- engine
 def lock_dir() -> tuple[str, bool]:
     """fit_lock_dir: the directory of the per-GPU launch lock file and whether it is the shared
@@ -462,6 +480,32 @@ class Engine:
                                      _ptr(out), C.byref(st)), "fit_place_device")
         return st.as_dict()
 
+    # ---- why a job does not fit ------------------------------------------
+    def explain(self, jobs):
+        """Every job judged alone against the current node table (fit_explain): a structured
+        array of WHY_DTYPE rows (code, need, members, fit, short_*).  Changes nothing."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        out = np.zeros(len(part), WHY_DTYPE)
+        check(lib().fit_explain(self._h, len(part), *[_ptr(c) for c in cols], _ptr(part), _ptr(k), _ptr(out)),
+              "fit_explain")
+        return out
+
+    def explain_device(self, cpu, mem, gpu, wall, part, nodes_k, out):
+        """All arguments torch tensors resident on this GPU; writes out (J rows of 8 int32, the
+        fields of WHY_DTYPE in order).  Returns the device time of its launches in ms (HIP events
+        on the context's stream, fit_explain_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_explain_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
+                                       _ptr(part), _ptr(nodes_k) if nodes_k is not None else None, _ptr(out)),
+              "fit_explain_device")
+        if j == 0:
+            return 0.0
+        ms = C.c_double()
+        check(lib().fit_explain_ms(self._h, C.byref(ms)), "fit_explain_ms")
+        return ms.value
+
     # ---- time-windowed backfill (DESIGN.md §2b) ------------------------------------------
     def load_timeline(self, tline):
         """Release events (synth.Timeline) over a horizon of tline.slots slots of tline.slot_min
@@ -576,6 +620,15 @@ class Admitter:
         r = (FitAdmitRes * n)()
         check(self._call(lambda h: lib().fit_admit_group(h, q, n, r)), "fit_admit_group")
         return [self._res(r[i], reqs[i][6]) for i in range(n)]
+
+    def explain(self, reqs: list[tuple]):
+        """fit_admitter_explain of (priority, cpu, mem, gpu, wall, part, k) requests (admit_group's
+        form) against the table the next batch would see, open reservations included: WHY_DTYPE rows."""
+        n = len(reqs)
+        q = (FitAdmitReq * max(n, 1))(*[FitAdmitReq(*r) for r in reqs])
+        out = np.zeros(n, WHY_DTYPE)
+        check(self._call(lambda h: lib().fit_admitter_explain(h, q, n, _ptr(out))), "fit_admitter_explain")
+        return out
 
     def load_nodes(self, nodes):
         cols = [np.ascontiguousarray(nodes.cpu_free, np.int32), np.ascontiguousarray(nodes.mem_free, np.int32),

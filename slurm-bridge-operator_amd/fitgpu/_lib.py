@@ -40,7 +40,8 @@ EXPORTS = [
     "fit_array_tasks", "fit_pod_demand", "fit_script_with_nodelist", "fit_partition_limits",
     "fit_node_columns", "fit_node_names", "fit_admitter_load_table", "fit_admitter_generation",
     "fit_admitter_script", "fit_set_max_array_size", "fit_release_events", "fit_set_watchdog_us",
-    "fit_lock_dir",
+    "fit_lock_dir", "fit_explain", "fit_explain_device", "fit_admitter_explain", "fit_why_message",
+    "fit_explain_ms",
 ]
 
 
@@ -86,6 +87,16 @@ FIT_REQ_ARRAY = 1  # fit_admit_req.flags: a task of an array job (never pinned)
 class FitAdmitRes(C.Structure):
     _fields_ = [("node", C.c_int32 * FIT_MAX_K), ("batch", C.c_int64), ("batch_jobs", C.c_int32),
                 ("order", C.c_int32), ("ticket", C.c_int64)]
+
+
+# fit_why.code (include/fitgpu.h), in order of precedence from PARTITION on; FITS last
+FIT_WHY_FITS, FIT_WHY_PARTITION, FIT_WHY_LIMIT_TIME, FIT_WHY_LIMIT_CPUS = 0, 1, 2, 3
+FIT_WHY_LIMIT_MEM, FIT_WHY_NO_NODES, FIT_WHY_RESOURCES = 4, 5, 6
+
+
+class FitWhy(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("code", "need", "members", "fit", "short_cpu", "short_mem", "short_gpu",
+                                         "short_time")]
 
 
 FIT_TABLE_STATE = 1  # fit_node_table.flags: part_mask carries node State (include/fitgpu.h)
@@ -147,6 +158,11 @@ def lib() -> C.CDLL:
         L.fit_load_partitions.argtypes = [P, i32, P, P, P]
         for name in ("fit_place", "fit_place_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, C.POINTER(FitStats)]
+        for name in ("fit_explain", "fit_explain_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P]
+        L.fit_admitter_explain.argtypes = [P, C.POINTER(FitAdmitReq), i32, P]
+        L.fit_why_message.argtypes = [C.POINTER(FitWhy), C.c_char_p, i32]
+        L.fit_explain_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

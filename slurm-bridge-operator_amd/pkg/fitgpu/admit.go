@@ -134,6 +134,48 @@ func (ad *Admitter) AdmitGroup(ds []Demand) ([]Admission, error) {
 	return out, nil
 }
 
+// Explain diagnoses the requests against the table the next batch would see, open reservations
+// included (fit_admitter_explain).  Safe for concurrent use; it does not queue behind the coalescer
+// and reserves nothing.
+func (ad *Admitter) Explain(ds []Demand) ([]Why, error) {
+	if len(ds) == 0 {
+		return nil, nil
+	}
+	reqs := make([]C.fit_admit_req, len(ds))
+	for i, d := range ds {
+		if d.NodesK > MaxK {
+			return nil, fmt.Errorf("fitgpu: nodes %d > %d", d.NodesK, MaxK)
+		}
+		reqs[i] = cReq(d)
+	}
+	rows := make([]C.fit_why, len(ds))
+	rc := C.fit_admitter_explain(ad.a, &reqs[0], C.int32_t(len(ds)), &rows[0])
+	runtime.KeepAlive(ad)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Why, len(ds))
+	for i := range rows {
+		out[i] = goWhy(&rows[i])
+	}
+	return out, nil
+}
+
+// WhyMessage is the row as one line in kube-scheduler's FailedScheduling shape (fit_why_message:
+// "0/6273 nodes fit now (need 2): 5120 insufficient cpu, 73 insufficient memory"); "" for a row
+// with an unknown code.
+func WhyMessage(w Why) string {
+	c := C.fit_why{code: C.int32_t(w.Code), need: C.int32_t(w.Need), members: C.int32_t(w.Members),
+		fit: C.int32_t(w.Fit), short_cpu: C.int32_t(w.ShortCPU), short_mem: C.int32_t(w.ShortMem),
+		short_gpu: C.int32_t(w.ShortGPU), short_time: C.int32_t(w.ShortTime)}
+	buf := make([]byte, 256)
+	n := C.fit_why_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
 // LoadNodes replaces the node table between batches (the node refresh ticker); open reservations
 // are taken from the new table again.
 func (ad *Admitter) LoadNodes(n Nodes) error {

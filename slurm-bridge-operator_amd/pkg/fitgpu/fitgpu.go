@@ -182,6 +182,66 @@ func (e *Engine) Place(j Jobs, kmax int) ([]int32, Stats, error) {
 	return out, st, check(rc)
 }
 
+// Why codes (fit_why.code, include/fitgpu.h): why a job does not fit, or that it does.
+const (
+	WhyFits      = int32(C.FIT_WHY_FITS)
+	WhyPartition = int32(C.FIT_WHY_PARTITION)
+	WhyLimitTime = int32(C.FIT_WHY_LIMIT_TIME)
+	WhyLimitCPUs = int32(C.FIT_WHY_LIMIT_CPUS)
+	WhyLimitMem  = int32(C.FIT_WHY_LIMIT_MEM)
+	WhyNoNodes   = int32(C.FIT_WHY_NO_NODES)
+	WhyResources = int32(C.FIT_WHY_RESOURCES)
+)
+
+// Why is one fit_why row: the job judged alone against the current node table.  The Short*
+// counts overlap, as kube-scheduler's do (a node short of two things is counted twice).
+type Why struct {
+	Code      int32 // Why*
+	Need      int32 // nodes the job needs (--nodes, at least 1)
+	Members   int32 // schedulable nodes of the job's partition
+	Fit       int32 // members the job fits on now
+	ShortCPU  int32
+	ShortMem  int32
+	ShortGPU  int32
+	ShortTime int32
+}
+
+func goWhy(w *C.fit_why) Why {
+	return Why{Code: int32(w.code), Need: int32(w.need), Members: int32(w.members), Fit: int32(w.fit),
+		ShortCPU: int32(w.short_cpu), ShortMem: int32(w.short_mem), ShortGPU: int32(w.short_gpu),
+		ShortTime: int32(w.short_time)}
+}
+
+// Explain diagnoses every job alone against the current node table (fit_explain); it changes
+// nothing.  NodesK may be empty, as for Place.
+func (e *Engine) Explain(j Jobs) ([]Why, error) {
+	cnt := len(j.CPU)
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part)) ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil
+	}
+	var nk *C.uint16_t
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	rows := make([]C.fit_why, cnt)
+	rc := C.fit_explain(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])), nk, &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Why, cnt)
+	for i := range rows {
+		out[i] = goWhy(&rows[i])
+	}
+	return out, nil
+}
+
 // PartitionFree is the allocation-aware replacement for GetPartitionCapacity's sum
 // (pkg/slurm-virtual-kubelet/node.go:183-190).
 func (e *Engine) PartitionFree(p int) (cpu, memMiB, gpu int64, err error) {

@@ -186,10 +186,39 @@ func (f *FitAdmission) admit(pod *v1.Pod) (string, []int64, error) {
 			as[0].Nodes, as[0].Batch, as[0].BatchJobs, pinned)
 		return out, tickets, nil
 	case as[0].Nodes[0] == fitgpu.Rejected:
-		return "", nil, fmt.Errorf("pod %s/%s exceeds the partition's limits", pod.Namespace, pod.Name)
+		return "", nil, fmt.Errorf("pod %s/%s exceeds the partition's limits%s", pod.Namespace, pod.Name, f.why(pod, ds))
 	default: // Unplaced: no node has room now; the library retries the pod
-		return "", nil, fmt.Errorf("pod %s/%s: no Slurm node of the partition fits it now", pod.Namespace, pod.Name)
+		return "", nil, fmt.Errorf("pod %s/%s: no Slurm node of the partition fits it now%s", pod.Namespace, pod.Name,
+			f.why(pod, ds))
 	}
+}
+
+// why is the reason a pod was not admitted, as ": <text>" for the end of admit's error — which
+// limit, or how many of the partition's nodes are short of cpus, memory, GPUs or walltime
+// (kube-scheduler's FailedScheduling text, which the pod lost when the fit moved here).  From an
+// Explain of the pod's first request (an array job's tasks are identical) against the table the
+// batch left.  The diagnosis never fails an admission: on an error it is logged and "" returned,
+// so the caller's text is the old one.
+func (f *FitAdmission) why(pod *v1.Pod, ds []fitgpu.Demand) string {
+	if len(ds) == 0 {
+		return ""
+	}
+	ws, err := f.adm.Explain(ds[:1])
+	if err != nil || len(ws) == 0 {
+		klog.Warningf("fit: no diagnosis for pod %s/%s: %v", pod.Namespace, pod.Name, err)
+		return ""
+	}
+	// a job can be unplaced in its batch and fit alone a moment later (a release in between, an
+	// array job whose tasks fit one by one but not together): "fits it now: 3/10 nodes fit now"
+	// would contradict itself, so that case keeps the old text; the pod is retried anyway
+	if ws[0].Code == fitgpu.WhyFits {
+		return ""
+	}
+	msg := fitgpu.WhyMessage(ws[0])
+	if msg == "" {
+		return ""
+	}
+	return ": " + msg
 }
 
 func (f *FitAdmission) release(tickets []int64) {
