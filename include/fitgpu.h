@@ -199,7 +199,7 @@ typedef struct {
 /* Host pointers; nodes_k may be NULL (= all 1).  j == 0 returns 0 whatever the pointers are.
  * FIT_E_INVAL: NULL ctx / arrays, a negative demand or nodes_k > FIT_MAX_K (the whole call fails,
  * as fit_place's does).  FIT_E_STATE: before fit_load_nodes; while a timeline is loaded (the
- * backfill view is fit_place_tl's start slot); on a context created with world > 1 or
+ * backfill view is fit_when's, or fit_place_tl's start slot); on a context created with world > 1 or
  * FIT_FLAG_COLLECTIVES (a rank holds no whole answer).  Three bounded launches, no persistent
  * grid: the call neither takes the per-GPU persistent-launch lock nor needs the watchdog. */
 int fit_explain(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
@@ -280,6 +280,61 @@ int fit_release_events(int32_t n, int32_t m, const int32_t* job_off, const int32
 /* Current timelines, dense [n][slots] per column, host pointers (n * slots entries each).  Slots
  * where a node is unusable, and nodes outside every partition, read -1. */
 int fit_read_timeline(fit_ctx* ctx, int32_t* cpu, int32_t* mem, int32_t* gpu);
+
+/* ---- when a pending job can start -----------------------------------------
+ * The backfill half of fit_explain's answer — `squeue --start`, `sbatch --test-only`: fit_when
+ * judges each of J jobs ALONE against the context's current timeline — the one fit_load_timeline
+ * built, minus every reservation fit_place_tl has committed since: what fit_read_timeline returns —
+ * and changes nothing: nothing is reserved, the order of the jobs does not matter.  A job takes one
+ * node (§2b).  One 32-byte row per job. */
+#define FIT_ETA_NOW 0         /* start == 0: a fit_place_tl of this job alone would start it now  */
+#define FIT_ETA_PARTITION 1   /* = FIT_WHY_PARTITION    these four: FIT_WHY_*'s numbers, rule and */
+#define FIT_ETA_LIMIT_TIME 2  /* = FIT_WHY_LIMIT_TIME   order — exactly the jobs fit_place_tl     */
+#define FIT_ETA_LIMIT_CPUS 3  /* = FIT_WHY_LIMIT_CPUS   marks FIT_REJECTED                        */
+#define FIT_ETA_LIMIT_MEM 4   /* = FIT_WHY_LIMIT_MEM                                              */
+#define FIT_ETA_NO_NODES 5    /* members == 0 (= FIT_WHY_NO_NODES)                                */
+#define FIT_ETA_LATER 6       /* start > 0                                                        */
+#define FIT_ETA_HORIZON 7     /* hosts == 0: no node has a start inside the horizon (dur > slots  */
+                              /* is one way to get here)                                          */
+/* Precedence: 1, 2, 3, 4, 5, 7, 6, 0 (first match wins).  For codes 1-4 every field but code and
+ * dur is 0, with start = node = wait_min = -1. */
+typedef struct {
+    int32_t code;      /* FIT_ETA_*                                                            */
+    int32_t dur;       /* max(1, ceil(wall / slot_min)) slots; set for every code             */
+    int32_t start;     /* the smallest earliest start slot over the members, -1 if none       */
+    int32_t node;      /* the node of the smallest §2b key (earliest start, then best fit,    */
+                       /* then node id), -1 if none: what fit_place_tl of this job alone      */
+                       /* would return                                                        */
+    int32_t wait_min;  /* start * slot_min, saturated at INT32_MAX; -1 if none                */
+    int32_t members;   /* nodes with the job's partition bit set                              */
+    int32_t hosts;     /* members that have any start inside the horizon                      */
+    int32_t now;       /* members whose earliest start is slot 0                              */
+} fit_eta;
+/* Host pointers.  j == 0 returns 0 whatever the pointers are.  FIT_E_INVAL: NULL ctx / arrays,
+ * j < 0, a negative demand (the whole call fails, as fit_place_tl's does).  FIT_E_STATE: before
+ * fit_load_nodes; without a timeline loaded; on a context created with world > 1 or
+ * FIT_FLAG_COLLECTIVES (a rank holds no whole answer).  Three bounded launches, no persistent grid:
+ * the call neither takes the per-GPU persistent-launch lock nor needs the watchdog. */
+int fit_when(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+             const int32_t* wall, const uint16_t* part, fit_eta* out);
+/* Same with device pointers (inputs resident in HBM, the rows written in HBM). */
+int fit_when_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                    const int32_t* wall, const uint16_t* part, fit_eta* out);
+/* Diagnostic, for measurement only (tools/when_bench.py): device time of the last successful
+ * fit_when_device on this context, in milliseconds (HIP events on the context's own stream around
+ * its launches).  FIT_E_STATE when there has been none. */
+int fit_when_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text, NUL-terminated into buf.  Host only: no device, no context.
+ * Returns the length written (without the NUL), or FIT_E_INVAL: NULL arguments, an unknown code,
+ * or a buffer too small for the text and its NUL (256 bytes always suffice).  The exact texts,
+ * <x> a decimal field of the row:
+ *   FIT_ETA_NOW         "can start now on <now>/<members> nodes"
+ *   FIT_ETA_LATER       "earliest start in <wait_min> min (slot <start>): <hosts>/<members> nodes
+ *                        can run it inside the horizon, none now"   — on one line
+ *   FIT_ETA_HORIZON     "no start inside the horizon on any of <members> nodes"
+ *   FIT_ETA_NO_NODES / LIMIT_TIME / LIMIT_CPUS / LIMIT_MEM / PARTITION: fit_why_message's texts of
+ *                       the codes with the same numbers, verbatim */
+int fit_when_message(const fit_eta* e, char* buf, int32_t buflen);
 
 /* ---- ingest / demand helpers (host code, mirrors of the reference Go functions) -------- */
 /* ParseDuration (pkg/slurm-agent/parse.go:36-109): 0 ok, FIT_E_UNLIMITED, FIT_E_PARSE. */

@@ -368,6 +368,11 @@ struct fit_ctx {
     DBuf<int32_t> ex_bad;
     HBuf<fit_why> h_ex;
     double ex_ms = -1;      // device time of the last fit_explain_device (fit_explain_ms)
+    // fit_when: the same three buffers and the same diagnostic
+    DBuf<fit_eta> wh_out;
+    DBuf<int32_t> wh_bad;
+    HBuf<fit_eta> h_wh;
+    double wh_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -470,6 +475,9 @@ struct fit_ctx {
         ex_out.release();
         ex_bad.release();
         h_ex.release();
+        wh_out.release();
+        wh_bad.release();
+        h_wh.release();
         h_x.release();
         xcount.release();
         h_count.release();
@@ -1528,6 +1536,63 @@ int check_explain_args(fit_ctx* c, int32_t j, const void* a, const void* b, cons
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_when
+// fit_explain's sequence over the run lists instead of the node rows —
+// classify, (a long queue: the jobs in component order), walk, finalise.  Bounded launches on the
+// context's stream, nothing waits on another workgroup.  Device pointers; *bad and the rows are
+// valid once the caller has drained the stream.
+static_assert(ETA_NOW == FIT_ETA_NOW && ETA_PARTITION == FIT_ETA_PARTITION && ETA_LIMIT_TIME == FIT_ETA_LIMIT_TIME &&
+                  ETA_LIMIT_CPUS == FIT_ETA_LIMIT_CPUS && ETA_LIMIT_MEM == FIT_ETA_LIMIT_MEM &&
+                  ETA_NO_NODES == FIT_ETA_NO_NODES && ETA_LATER == FIT_ETA_LATER && ETA_HORIZON == FIT_ETA_HORIZON,
+              "fit_device.h and fitgpu.h disagree");
+static_assert(FIT_ETA_PARTITION == FIT_WHY_PARTITION && FIT_ETA_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
+                  FIT_ETA_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && FIT_ETA_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
+                  FIT_ETA_NO_NODES == FIT_WHY_NO_NODES,
+              "FIT_ETA_1..5 are FIT_WHY_1..5");
+static_assert(sizeof(fit_eta) == 32, "fit_eta is 32 bytes");
+// nodes a wave walks at least before the node range is sliced further (explain_slices; fit_explain
+// keeps 32 rows): a node costs a header load and a dependent load per four runs, so a short batch
+// is latency-bound and wants the waves — 1,024 jobs on C5: 0.307 ms at 32, DESIGN.md §3.12 at 4
+constexpr int kWhenMinNodes = 4;
+
+int when_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+              const int32_t* wall, const uint16_t* part, fit_eta* out, int32_t* bad) {
+    const int C = c->ncomp;
+    hipStream_t st = c->st;
+    if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    HIP_TRY(launch_when_classify(st, c->d_ptab.p, c->np, cpu, mem, gpu, wall, part, J, c->tl_slot_min, out,
+                                 c->jcomp.p, bad));
+    const int32_t *jl = nullptr, *live = nullptr;
+    if (J > kExplainSortJobs && C > 1) {
+        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
+            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
+            return FIT_E_OOM;
+        int32_t* g = c->jls.p + joblists_scratch_ints(J);
+        int32_t* jbd = g + 2;
+        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
+        jl = c->jl.p;
+        live = jbd + C;  // jobs that have a component
+    }
+    ExplainComps ec;
+    ec.ncomp = C;
+    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+    HIP_TRY(launch_when(st, c->tlhdr.p, c->slab.p, ec, c->tl_slots, c->tl_slot_min, cpu, mem, gpu, part, J,
+                        c->jcomp.p, jl, live, explain_slices(J, c->cls_maxn, c->cus, kWhenMinNodes), out));
+    return 0;
+}
+
+int check_when_args(fit_ctx* c, int32_t j, const void* a, const void* b, const void* d, const void* e,
+                    const void* f, const void* out) {
+    if (!c) return fail(FIT_E_INVAL, "null ctx");
+    if (j < 0) return fail(FIT_E_INVAL, "j=%d", j);
+    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
+    if (c->collective()) return fail(FIT_E_STATE, "fit_when on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
+    if (!c->have_tl) return fail(FIT_E_STATE, "fit_load_timeline not called");
+    if (j > 0 && (!a || !b || !d || !e || !f || !out)) return fail(FIT_E_INVAL, "bad job arrays");
+    return 0;
+}
+
 int load_timeline_impl(fit_ctx* c, int32_t slots, int32_t slot_min, int64_t ne) {
     if (c->tlhdr.ensure(std::max(c->nn, 1)) ||
         c->slab.ensure((size_t)std::max(c->nn, 1) * TL_MAX_SLOTS) || c->tl_err.ensure(1) ||
@@ -1927,6 +1992,64 @@ int fit_explain_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->ex_ms < 0) return fail(FIT_E_STATE, "no fit_explain_device yet");
     *ms = c->ex_ms;
+    return 0;
+}
+
+int fit_when(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+             const int32_t* wall, const uint16_t* part, fit_eta* out) {
+    int rc = check_when_args(c, j, cpu, mem, gpu, wall, part, out);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the columns packed in pinned memory, ONE copy to the device (as fit_explain)
+    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j;
+    const size_t tot = 4 * b + bh;
+    if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot) || c->wh_out.ensure((size_t)j + 1) ||
+        c->h_wh.ensure((size_t)j + 1))
+        return FIT_E_OOM;
+    uint8_t* h = c->h_jpack.p;
+    memcpy(h, cpu, b);
+    memcpy(h + b, mem, b);
+    memcpy(h + 2 * b, gpu, b);
+    memcpy(h + 3 * b, wall, b);
+    memcpy(h + 4 * b, part, bh);
+    HIP_TRY(hipMemcpyAsync(c->jpack.p, h, tot, hipMemcpyHostToDevice, c->st));
+    const uint8_t* d = c->jpack.p;
+    // the flag word behind the rows: rows and flag come back in ONE copy
+    int32_t* bad = reinterpret_cast<int32_t*>(c->wh_out.p + j);
+    rc = when_impl(c, j, (const int32_t*)d, (const int32_t*)(d + b), (const int32_t*)(d + 2 * b),
+                   (const int32_t*)(d + 3 * b), (const uint16_t*)(d + 4 * b), c->wh_out.p, bad);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_wh.p, c->wh_out.p, sizeof(fit_eta) * ((size_t)j + 1), hipMemcpyDeviceToHost,
+                           c->st));
+    HIP_TRY(j <= SMALL_ARGJ ? sync_small(c) : hipStreamSynchronize(c->st));
+    if (c->h_wh.p[j].code) return fail(FIT_E_INVAL, "a job has a negative demand");
+    memcpy(out, c->h_wh.p, sizeof(fit_eta) * j);
+    return 0;
+}
+
+int fit_when_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                    const int32_t* wall, const uint16_t* part, fit_eta* out) {
+    int rc = check_when_args(c, j, cpu, mem, gpu, wall, part, out);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->wh_bad.ensure(1) || c->h_wh.ensure(1)) return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], c->st));
+    rc = when_impl(c, j, cpu, mem, gpu, wall, part, out, c->wh_bad.p);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], c->st));
+    HIP_TRY(hipMemcpyAsync(c->h_wh.p, c->wh_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->h_wh.p[0].code) return fail(FIT_E_INVAL, "a job has a negative demand");
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->wh_ms = ms;
+    return 0;
+}
+
+int fit_when_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->wh_ms < 0) return fail(FIT_E_STATE, "no fit_when_device yet");
+    *ms = c->wh_ms;
     return 0;
 }
 

@@ -179,7 +179,28 @@ hipError_t launch_explain(hipStream_t st, const NodeRec* rec, const ExplainComps
                           const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                           int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
                           void* out);
-int explain_slices(int32_t nj, int32_t maxn, int cus);
+int explain_slices(int32_t nj, int32_t maxn, int cus, int min_rows = 32);
+
+// ---- fit_when (fit_when.hip) -------------------------------------------
+// The codes of include/fitgpu.h FIT_ETA_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
+enum EtaCode : int32_t {
+    ETA_NOW = 0,
+    ETA_PARTITION = 1,
+    ETA_LIMIT_TIME = 2,
+    ETA_LIMIT_CPUS = 3,
+    ETA_LIMIT_MEM = 4,
+    ETA_NO_NODES = 5,
+    ETA_LATER = 6,
+    ETA_HORIZON = 7,
+};
+hipError_t launch_when_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                const uint16_t* jpart, int32_t nj, int32_t slot_min, void* out, int8_t* jcomp,
+                                int32_t* bad);
+hipError_t launch_when(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                       int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                       const uint16_t* jpart, int32_t nj, const int8_t* jcomp, const int32_t* jl,
+                       const int32_t* live, int slices, void* out);
 
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {

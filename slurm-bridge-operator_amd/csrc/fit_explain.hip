@@ -187,12 +187,12 @@ hipError_t launch_explain(hipStream_t st, const NodeRec* rec, const ExplainComps
 }
 
 // Node slices for nj jobs against components of at most maxn rows: enough workgroups to fill the
-// chip (8 per CU) while a wave still walks EX_MIN_ROWS rows; 1 for a long queue.
-int explain_slices(int32_t nj, int32_t maxn, int cus) {
-    constexpr int EX_MIN_ROWS = 32;
+// chip (8 per CU) while a wave still walks min_rows rows (32 here; fit_when's walk costs far more
+// per row and asks for fewer); 1 for a long queue.
+int explain_slices(int32_t nj, int32_t maxn, int cus, int min_rows) {
     const int64_t tiles = (nj + EX_JOBS - 1) / EX_JOBS;
     const int64_t want = ((int64_t)cus * 8 + tiles - 1) / std::max<int64_t>(tiles, 1);
-    const int64_t most = ((int64_t)maxn + EX_WAVES * EX_MIN_ROWS - 1) / (EX_WAVES * EX_MIN_ROWS);
+    const int64_t most = ((int64_t)maxn + EX_WAVES * min_rows - 1) / (EX_WAVES * min_rows);
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(want, most), 4096));
 }
 

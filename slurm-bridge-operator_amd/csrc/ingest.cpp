@@ -941,4 +941,38 @@ int fit_why_message(const fit_why* w, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_eta row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
+// with the same numbers and take its sentences.  No device, no context.
+int fit_when_message(const fit_eta* e, char* buf, int32_t buflen) {
+    if (!e || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    switch (e->code) {
+        case FIT_ETA_PARTITION:
+        case FIT_ETA_LIMIT_TIME:
+        case FIT_ETA_LIMIT_CPUS:
+        case FIT_ETA_LIMIT_MEM:
+        case FIT_ETA_NO_NODES: {
+            fit_why w;
+            memset(&w, 0, sizeof w);
+            w.code = e->code;
+            return fit_why_message(&w, buf, buflen);
+        }
+        case FIT_ETA_NOW:
+            s = "can start now on " + std::to_string(e->now) + "/" + std::to_string(e->members) + " nodes";
+            break;
+        case FIT_ETA_LATER:
+            s = "earliest start in " + std::to_string(e->wait_min) + " min (slot " + std::to_string(e->start) +
+                "): " + std::to_string(e->hosts) + "/" + std::to_string(e->members) +
+                " nodes can run it inside the horizon, none now";
+            break;
+        case FIT_ETA_HORIZON:
+            s = "no start inside the horizon on any of " + std::to_string(e->members) + " nodes";
+            break;
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 }  // extern "C"

@@ -32,7 +32,9 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_XCHG_MAX_I32, FIT_XCHG_MIN_I32, FIT_XCHG_MIN_U64, XCHG_FN, FitAdmitReq, FitAdmitRes, FitError,
                    FitJobResources, FitNode, FitNodeTable, FitOpts, FitPodLabels, FitResources, FitStats, check, lib,
                    FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
-                   FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy)
+                   FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy,
+                   FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
+                   FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -44,6 +46,8 @@ __all__ = [
     "partition_limits", "node_columns", "POD_LABEL_KEYS", "node_names", "set_max_array_size", "FIT_TABLE_STATE",
     "FIT_TABLE_PIN", "why_message", "WHY_DTYPE", "FIT_WHY_FITS", "FIT_WHY_PARTITION", "FIT_WHY_LIMIT_TIME",
     "FIT_WHY_LIMIT_CPUS", "FIT_WHY_LIMIT_MEM", "FIT_WHY_NO_NODES", "FIT_WHY_RESOURCES",
+    "when_message", "ETA_DTYPE", "FIT_ETA_NOW", "FIT_ETA_PARTITION", "FIT_ETA_LIMIT_TIME", "FIT_ETA_LIMIT_CPUS",
+    "FIT_ETA_LIMIT_MEM", "FIT_ETA_NO_NODES", "FIT_ETA_LATER", "FIT_ETA_HORIZON",
 ]
 
 
@@ -346,6 +350,21 @@ def why_message(row) -> str:
     return buf.raw[:n].decode()
 
 
+# ---------------------------------------------------------------------------------- when
+# one fit_eta row (include/fitgpu.h), 32 bytes: what Engine.when returns
+ETA_DTYPE = np.dtype([(n, np.int32) for n, _ in FitEta._fields_])
+
+
+def when_message(row) -> str:
+    """A fit_eta row (an element of a when() result, or any mapping / object with its fields) as
+    one line of text (fit_when_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    e = FitEta(*(int(get(n)) for n, _ in FitEta._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_when_message(C.byref(e), buf, len(buf)), "fit_when_message")
+    return buf.raw[:n].decode()
+
+
 # ------------------------------------------------------------------------------- engine
 def lock_dir() -> tuple[str, bool]:
     """fit_lock_dir: the directory of the per-GPU launch lock file and whether it is the shared
@@ -542,6 +561,30 @@ class Engine:
         check(lib().fit_place_tl_device(self._h, int(cpu.numel()), *[_ptr(t) for t in (cpu, mem, gpu, wall, part)],
                                         _ptr(out_node), _ptr(out_start), C.byref(st)), "fit_place_tl_device")
         return st.as_dict()
+
+    # ---- when a pending job can start ------------------------------------
+    def when(self, jobs):
+        """Every job judged alone against the current timeline (fit_when): a structured array of
+        ETA_DTYPE rows (code, dur, start, node, wait_min, members, hosts, now).  Changes nothing;
+        jobs.nodes_k plays no part (a backfill job takes one node)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        out = np.zeros(len(part), ETA_DTYPE)
+        check(lib().fit_when(self._h, len(part), *[_ptr(c) for c in cols], _ptr(part), _ptr(out)), "fit_when")
+        return out
+
+    def when_device(self, cpu, mem, gpu, wall, part, out):
+        """All arguments torch tensors resident on this GPU; writes out (J rows of 8 int32, the
+        fields of ETA_DTYPE in order).  Returns the device time of its launches in ms (HIP events
+        on the context's stream, fit_when_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_when_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part), _ptr(out)),
+              "fit_when_device")
+        if j == 0:
+            return 0.0
+        ms = C.c_double()
+        check(lib().fit_when_ms(self._h, C.byref(ms)), "fit_when_ms")
+        return ms.value
 
     def read_timeline(self):
         """Dense [n, slots, 3] int32 (cpu, mem, gpu)."""

@@ -41,7 +41,7 @@ EXPORTS = [
     "fit_node_columns", "fit_node_names", "fit_admitter_load_table", "fit_admitter_generation",
     "fit_admitter_script", "fit_set_max_array_size", "fit_release_events", "fit_set_watchdog_us",
     "fit_lock_dir", "fit_explain", "fit_explain_device", "fit_admitter_explain", "fit_why_message",
-    "fit_explain_ms",
+    "fit_explain_ms", "fit_when", "fit_when_device", "fit_when_ms", "fit_when_message",
 ]
 
 
@@ -97,6 +97,15 @@ FIT_WHY_LIMIT_MEM, FIT_WHY_NO_NODES, FIT_WHY_RESOURCES = 4, 5, 6
 class FitWhy(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("code", "need", "members", "fit", "short_cpu", "short_mem", "short_gpu",
                                          "short_time")]
+
+
+# fit_eta.code (include/fitgpu.h): 1-5 are FIT_WHY_*'s; precedence 1, 2, 3, 4, 5, 7, 6, 0
+FIT_ETA_NOW, FIT_ETA_PARTITION, FIT_ETA_LIMIT_TIME, FIT_ETA_LIMIT_CPUS = 0, 1, 2, 3
+FIT_ETA_LIMIT_MEM, FIT_ETA_NO_NODES, FIT_ETA_LATER, FIT_ETA_HORIZON = 4, 5, 6, 7
+
+
+class FitEta(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("code", "dur", "start", "node", "wait_min", "members", "hosts", "now")]
 
 
 FIT_TABLE_STATE = 1  # fit_node_table.flags: part_mask carries node State (include/fitgpu.h)
@@ -163,6 +172,10 @@ def lib() -> C.CDLL:
         L.fit_admitter_explain.argtypes = [P, C.POINTER(FitAdmitReq), i32, P]
         L.fit_why_message.argtypes = [C.POINTER(FitWhy), C.c_char_p, i32]
         L.fit_explain_ms.argtypes = [P, C.POINTER(C.c_double)]
+        for name in ("fit_when", "fit_when_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
+        L.fit_when_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_when_message.argtypes = [C.POINTER(FitEta), C.c_char_p, i32]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

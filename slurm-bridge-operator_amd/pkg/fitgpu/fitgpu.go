@@ -342,6 +342,76 @@ func (e *Engine) PlaceBackfill(j Jobs) (node, start []int32, st Stats, err error
 	return node, start, st, check(rc)
 }
 
+// Eta codes (fit_eta.code, include/fitgpu.h): when a job can start.  EtaPartition .. EtaNoNodes
+// are WhyPartition .. WhyNoNodes.
+const (
+	EtaNow       = int32(C.FIT_ETA_NOW)
+	EtaPartition = int32(C.FIT_ETA_PARTITION)
+	EtaLimitTime = int32(C.FIT_ETA_LIMIT_TIME)
+	EtaLimitCPUs = int32(C.FIT_ETA_LIMIT_CPUS)
+	EtaLimitMem  = int32(C.FIT_ETA_LIMIT_MEM)
+	EtaNoNodes   = int32(C.FIT_ETA_NO_NODES)
+	EtaLater     = int32(C.FIT_ETA_LATER)
+	EtaHorizon   = int32(C.FIT_ETA_HORIZON)
+)
+
+// Eta is one fit_eta row: the job judged alone against the current timeline (DESIGN.md §2d).
+type Eta struct {
+	Code    int32 // Eta*
+	Dur     int32 // slots the job occupies: max(1, ceil(WallMin / slotMin))
+	Start   int32 // earliest start slot over the partition's nodes, -1 if none
+	Node    int32 // the node PlaceBackfill of this job alone would return, -1 if none
+	WaitMin int32 // Start * slotMin, -1 if none
+	Members int32 // schedulable nodes of the job's partition
+	Hosts   int32 // members with a start inside the horizon
+	Now     int32 // members that can start it at slot 0
+}
+
+func goEta(r *C.fit_eta) Eta {
+	return Eta{Code: int32(r.code), Dur: int32(r.dur), Start: int32(r.start), Node: int32(r.node),
+		WaitMin: int32(r.wait_min), Members: int32(r.members), Hosts: int32(r.hosts), Now: int32(r.now)}
+}
+
+// When gives every job, judged alone against the current timeline (LoadTimeline minus the
+// reservations of every PlaceBackfill since), its earliest start and node (fit_when: `squeue
+// --start`); it reserves nothing.  NodesK is not read: a backfill job takes one node.
+func (e *Engine) When(j Jobs) ([]Eta, error) {
+	cnt := len(j.CPU)
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part)) {
+		return nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil
+	}
+	rows := make([]C.fit_eta, cnt)
+	rc := C.fit_when(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])), &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Eta, cnt)
+	for i := range rows {
+		out[i] = goEta(&rows[i])
+	}
+	return out, nil
+}
+
+// WhenMessage is the row as one line (fit_when_message: "earliest start in 35 min (slot 7): 12/40
+// nodes can run it inside the horizon, none now"); "" for a row with an unknown code.
+func WhenMessage(t Eta) string {
+	c := C.fit_eta{code: C.int32_t(t.Code), dur: C.int32_t(t.Dur), start: C.int32_t(t.Start),
+		node: C.int32_t(t.Node), wait_min: C.int32_t(t.WaitMin), members: C.int32_t(t.Members),
+		hosts: C.int32_t(t.Hosts), now: C.int32_t(t.Now)}
+	buf := make([]byte, 256)
+	n := C.fit_when_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
 // IngestNodes turns `scontrol show nodes` output into the engine's node table (Client.Nodes +
 // parseNode, pkg/slurm-agent/slurm.go:354-363 / parse.go:291-308, plus Gres/GresUsed, State,
 // Partitions and NodeName), partitions[p] = the partition of part_mask bit p.
