@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <new>
@@ -28,109 +29,16 @@
 #include "../../include/fitgpu.h"
 #include "fit_device.h"
 
-namespace fitgpu {
-hipError_t launch_scan(int blocks, hipStream_t st, const NodeRec* rec, const int32_t* jl,
-                       const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
-                       const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
-                       const CompPlan* plan, int ncomp, uint64_t* cand, uint64_t* bnd,
-                       JobRec* wjob);
-hipError_t launch_commit(int ncomp, int epl, size_t lds_bytes, hipStream_t st, NodeRec* rec,
-                         const CompPlan* plan, const uint64_t* cand, int64_t rank_stride,
-                         int nranks, const uint64_t* bnd, const JobRec* wjob, int32_t* out,
-                         int kmax, CommitResult* res);
-hipError_t launch_prefilter(hipStream_t st, const int32_t* jcpu, const int32_t* jmem,
-                            const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
-                            int32_t nj, int32_t kmax, const int32_t* ptab, int32_t np,
-                            int32_t* out, int8_t* jcomp);
-size_t joblists_scratch_ints(int32_t nj);
-hipError_t launch_joblists(hipStream_t st, const int8_t* jcomp, int32_t nj, int ncomp,
-                           int32_t* scratch, int32_t* g, int32_t* jb, int32_t* mb, int32_t* jl,
-                           int32_t* jpk);
-hipError_t launch_small_args(hipStream_t st, int ncomp, NodeRec* rec, const SmallComps& C, const int32_t* ptab,
-                             int32_t np, const SmallBatch& B, bool has_nk, int32_t nj, int32_t kmax, int32_t* out,
-                             int32_t* stat);
-hipError_t launch_small(hipStream_t st, int ncomp, NodeRec* rec, const SmallComps& C,
-                        const int32_t* ptab, int32_t np, const int32_t* jcpu, const int32_t* jmem,
-                        const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
-                        const uint16_t* jk, int32_t nj, int32_t kmax, int32_t* out, int32_t* stat);
-hipError_t launch_gather_nodes(hipStream_t st, const int32_t* cpu, const int32_t* mem,
-                               const int32_t* gpu, const int32_t* av, const uint32_t* mask,
-                               const int32_t* perm, int32_t nn, NodeRec* rec);
-hipError_t launch_scatter_nodes(hipStream_t st, const NodeRec* rec, int32_t nn, int32_t* cpu,
-                                int32_t* mem, int32_t* gpu);
-size_t engine_lds_bytes(int32_t max_component_nodes);
-// demand-class engine (fit_class.hip)
-size_t class_lds_bytes(int32_t max_component_nodes);
-int class_max();
-int class_table_slots();
-size_t class_slot_bytes();
-int class_max_nodes();
-hipError_t launch_classify(hipStream_t st, const int8_t* jcomp, const int32_t* jcpu, const int32_t* jmem,
-                           const int32_t* jgpu, const uint16_t* jpart, int32_t nj, void* tab, int4* dem,
-                           int32_t* ncls, int16_t* jcls);
-hipError_t launch_class(hipStream_t st, int ncomp, size_t lds, NodeRec* rec, const int32_t* nbv, uint32_t owned,
-                        const int32_t* jb, const int32_t* jl, const int32_t* jwall, const uint16_t* jk,
-                        const int16_t* jcls, const int4* dem, const int32_t* ncls, int32_t kmax, int32_t* out,
-                        CompOut* co, unsigned* err);
-hipError_t launch_class_out(hipStream_t st, int32_t* out, int64_t n, const NodeRec* rec);
-size_t engine_ctl_bytes();
-size_t engine_ctl_error_offset();
-size_t engine_ctl_trip_offset();
-size_t engine_ring_bytes();
-size_t engine_ring_tasks();
-int engine_ring_groups();
+using namespace fitgpu;
+
+namespace {
+
 // components sharing the fullest task ring (fit_engine_ctl.h: component c goes to ring
 // c % min(groups, nc))
 inline int64_t ring_comps(int nc) {
     const int g = std::max(1, std::min(engine_ring_groups(), nc));
     return (nc + g - 1) / g;
 }
-int engine_blocks_per_cu(size_t lds);
-hipError_t launch_engine(int blocks, size_t lds, hipStream_t st, void* ctl, void* ring,
-                         const void* cs, void* co, CompPlan* plans, int ncomp, NodeRec* rec,
-                         const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
-                         const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
-                         const uint16_t* jk, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
-                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd);
-// time-windowed backfill (fit_timeline.hip)
-hipError_t launch_build_tl(hipStream_t st, const int32_t* cpu, const int32_t* mem,
-                           const int32_t* gpu, const int32_t* av, const uint32_t* mask,
-                           const int32_t* perm, int32_t nn, int32_t H, int32_t slot_min,
-                           const int32_t* off, const int32_t* rs, const int32_t* rc,
-                           const int32_t* rm, const int32_t* rg, Seg* slab, TlHdr* hdr,
-                           uint32_t* err);
-hipError_t launch_scan_tl(int blocks, hipStream_t st, const Seg* slab, const TlHdr* hdr,
-                          const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
-                          const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
-                          const CompPlan* plan, int ncomp, uint64_t* cand, uint64_t* bnd,
-                          JobRec* wjob, int32_t H, int32_t slot_min);
-size_t commit_tl_lds_bytes(int32_t max_component_nodes);
-int commit_tl_runs(int32_t max_component_nodes);
-hipError_t launch_commit_tl(int ncomp, int epl, size_t lds, hipStream_t st, Seg* slab,
-                            TlHdr* hdr, const CompPlan* plan, const uint64_t* cand,
-                            int64_t rank_stride, int nranks, const uint64_t* bnd,
-                            const JobRec* wjob, const int32_t* perm, int32_t* out, int32_t* outs,
-                            CommitResult* res, int32_t H, int32_t R);
-int engine_tl_runs(int32_t max_component_nodes);
-size_t engine_tl_lds_bytes(int32_t max_component_nodes);
-int engine_tl_blocks_per_cu(size_t lds, int mode);
-size_t engine_tl_scan_lds_bytes();
-hipError_t launch_engine_tl(int blocks, size_t lds, hipStream_t st, void* ctl, void* ring,
-                            const void* cs, void* co, CompPlan* plans, int ncomp, Seg* slab,
-                            TlHdr* hdr, const int32_t* jl, const int32_t* jcpu,
-                            const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
-                            const uint16_t* jpart, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
-                            const int32_t* perm, int32_t* out, int32_t* outs, int32_t H,
-                            int32_t slot_min, int32_t R, int64_t* wbusy, int mode,
-                            unsigned* resident, unsigned wd);
-hipError_t launch_expand_tl(hipStream_t st, const int32_t* perm, const Seg* slab,
-                            const TlHdr* hdr, int32_t nn, int32_t H, int32_t* oc, int32_t* om,
-                            int32_t* og);
-}  // namespace fitgpu
-
-using namespace fitgpu;
-
-namespace {
 
 thread_local std::string g_last_error;
 
@@ -159,7 +67,7 @@ int fail(int code, const char* fmt, ...) {
             return fail(FIT_E_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r_));        \
     } while (0)
 
-// device buffer that only grows
+// device buffer that only grows; owns its memory
 template <class T>
 struct DBuf {
     T* p = nullptr;
@@ -182,6 +90,10 @@ struct DBuf {
         p = nullptr;
         cap = 0;
     }
+    DBuf() = default;
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() { release(); }
 };
 
 template <class T>
@@ -206,6 +118,21 @@ struct HBuf {  // pinned host buffer
         p = nullptr;
         cap = 0;
     }
+    HBuf() = default;
+    HBuf(const HBuf&) = delete;
+    HBuf& operator=(const HBuf&) = delete;
+    ~HBuf() { release(); }
+};
+
+// fit_explain / fit_when: the rows on the device (host entry point; the flag word rides behind
+// them), the flag word of the device entry point, the pinned copy both come back into, and the
+// device time of the last *_device call (fit_explain_ms / fit_when_ms)
+template <class Row>
+struct QueryBufs {
+    DBuf<Row> out;
+    DBuf<int32_t> bad;
+    HBuf<Row> h;
+    double ms = -1;
 };
 
 int find_root(int* par, int x) {
@@ -316,11 +243,34 @@ struct ArbGuard {
 
 }  // namespace
 
-struct fit_ctx {
+// The context's runtime handles.  A base of fit_ctx, so they go after every buffer member has
+// freed its memory: events, the mapped flag, the streams, then the communicator.
+struct CtxHandles {
+    ncclComm_t comm = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[6] = {};
+    // FIT_TL_SPLIT: the backfill engine's scan workers as a second, concurrent launch
+    hipStream_t st2 = nullptr;
+    hipEvent_t ev_join = nullptr;
+    unsigned* resident = nullptr;  // host-mapped: committer blocks running
+    CtxHandles() = default;
+    CtxHandles(const CtxHandles&) = delete;
+    CtxHandles& operator=(const CtxHandles&) = delete;
+    ~CtxHandles() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (resident) (void)hipHostFree(resident);
+        if (st2) (void)hipStreamDestroy(st2);
+        if (st) (void)hipStreamDestroy(st);
+        if (comm) (void)ncclCommDestroy(comm);
+    }
+};
+
+struct fit_ctx : CtxHandles {
     int device = 0;
     int rank = 0, world = 1;
     int shard_mode = FIT_SHARD_AUTO;
-    ncclComm_t comm = nullptr;
     fit_exchange_fn xchg = nullptr;  // host exchange instead of RCCL (tests, custom transport)
     void* xchg_user = nullptr;
     HBuf<uint8_t> h_x;               // staging for the host exchange
@@ -362,17 +312,10 @@ struct fit_ctx {
     HBuf<int32_t> h_small;
     DBuf<uint8_t> jpack;    // fit_place's job columns of a small batch, packed: one H2D copy
     HBuf<uint8_t> h_jpack;
-    // fit_explain: the rows on the device (host entry point; the flag word rides behind them), the
-    // flag word of the device entry point, and the pinned copy both come back into
-    DBuf<fit_why> ex_out;
-    DBuf<int32_t> ex_bad;
-    HBuf<fit_why> h_ex;
-    double ex_ms = -1;      // device time of the last fit_explain_device (fit_explain_ms)
-    // fit_when: the same three buffers and the same diagnostic
-    DBuf<fit_eta> wh_out;
-    DBuf<int32_t> wh_bad;
-    HBuf<fit_eta> h_wh;
-    double wh_ms = -1;
+    // fit_explain / fit_when: the rows on the device, the device entry point's flag word, the
+    // pinned copy and the *_ms diagnostic of each
+    QueryBufs<fit_why> ex;
+    QueryBufs<fit_eta> wh;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -386,12 +329,6 @@ struct fit_ctx {
     DBuf<NodeRec> rec_bak;           // node rows before a persistent launch (restored on a trip)
     unsigned wd_ticks = 1000000000u; // watchdog: realtime ticks (10 ns) a wait may last (10 s)
     HBuf<uint64_t> h_count;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[6] = {};
-    // FIT_TL_SPLIT: the backfill engine's scan workers as a second, concurrent launch
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_join = nullptr;
-    unsigned* resident = nullptr;  // host-mapped: committer blocks running
     int wmin = 256, wmax = 8192;
 
     // node table
@@ -435,71 +372,6 @@ struct fit_ctx {
     DBuf<int32_t> outs, rel_off, rel_slot, rel_cpu, rel_mem, rel_gpu;
     DBuf<uint32_t> tl_err;
     HBuf<uint32_t> h_tl_err;
-
-    ~fit_ctx() {
-        for (auto* b : {&col_cpu, &col_mem, &col_gpu, &col_av, &perm, &jcpu, &jmem, &jgpu,
-                        &jwall, &out, &jl, &jpk, &rb_cpu, &rb_mem, &rb_gpu})
-            b->release();
-        rec.release();
-        tlhdr.release();
-        for (auto* b : {&outs, &rel_off, &rel_slot, &rel_cpu, &rel_mem, &rel_gpu})
-            b->release();
-        slab.release();
-        tl_err.release();
-        h_tl_err.release();
-        col_mask.release();
-        d_ptab.release();
-        jpart.release();
-        jk.release();
-        jcomp.release();
-        cand.release();
-        bnd.release();
-        wjob.release();
-        plan.release();
-        res.release();
-        h_plan.release();
-        h_res.release();
-        jls.release();
-        h_jls.release();
-        jcls.release();
-        cls_tab.release();
-        cls_dem.release();
-        cls_n.release();
-        cls_err.release();
-        h_cls_n.release();
-        h_cls_err.release();
-        small_placed.release();
-        h_small.release();
-        jpack.release();
-        h_jpack.release();
-        ex_out.release();
-        ex_bad.release();
-        h_ex.release();
-        wh_out.release();
-        wh_bad.release();
-        h_wh.release();
-        h_x.release();
-        xcount.release();
-        h_count.release();
-        ectl.release();
-        ering.release();
-        ecs.release();
-        eco.release();
-        ebusy.release();
-        h_ecs.release();
-        h_eco.release();
-        h_ebusy.release();
-        h_err.release();
-        h_trip.release();
-        rec_bak.release();
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (resident) (void)hipHostFree(resident);
-        if (st2) (void)hipStreamDestroy(st2);
-        if (st) (void)hipStreamDestroy(st);
-        if (comm) (void)ncclCommDestroy(comm);
-    }
 };
 
 namespace {
@@ -651,144 +523,32 @@ int trip_error(fit_ctx* c, const char* engine) {
                 t.block, t.q_head, t.q_tail, t.pubt, t.tdone, t.need, t.waited / 1e5, t.when / 1e5,
                 c->wd_ticks / 1e5);
 }
-// All rounds of all owned components in one launch (fit_persistent.hip, DESIGN.md §3.6).
-int run_persistent(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector<char>& owned,
-                   const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* wall,
-                   const uint16_t* part, const uint16_t* nk, int32_t* out, int32_t kmax,
-                   fit_stats& S) {
-    const int C = c->ncomp;
-    hipStream_t st = c->st;
+// ---- what the two persistent engines (k_engine, k_engine_tl) share on the host ----------------
+// The launch's components: those with jobs that this rank owns, launch component i = comps[i].
+struct EngineComps {
     std::vector<int> comps;
-    int32_t maxnodes = 0;
-    for (int k = 0; k < C; ++k)
+    int nc = 0;
+    int32_t maxnodes = 0;  // largest of them (nodes)
+    int64_t wcap = 0;      // window cap: the engines' per-tile counters hold 128 job tiles
+};
+
+EngineComps engine_comps(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector<char>& owned) {
+    EngineComps E;
+    for (int k = 0; k < c->ncomp; ++k)
         if (owned[k] && jb[k + 1] > jb[k]) {
-            comps.push_back(k);
-            maxnodes = std::max(maxnodes, c->nb[k + 1] - c->nb[k]);
+            E.comps.push_back(k);
+            E.maxnodes = std::max(E.maxnodes, c->nb[k + 1] - c->nb[k]);
         }
-    const int nc = (int)comps.size();
-    if (nc == 0) return 0;
-    const int64_t wcap = std::min(c->wmax, 8192);  // k_engine's per-tile counters: 128 job tiles
-    const int64_t per_comp_cand = wcap * MAX_SLICES * KS;
-    // keys per block-slice: KS, halved (slices doubled, the same MAX_SLICES * KS candidates per
-    // job) while a wave's sub-slice would exceed sub_target nodes — a round's first job tile, which
-    // the commit waits for, then spreads over more blocks.  C3o (one 100k-node component): KS 16
-    // 552 ms, 8 471 ms, 4 441 ms, 2 480 ms (the bound B, a minimum over more slices of fewer keys,
-    // turns tight: 891 rescans); C3 / C2 components stay at KS (sub-slices of 98 / 64 nodes).
-    int sub_target = 256, ks_min = 4;
-    if (const char* e = getenv("FIT_SUB_TARGET")) sub_target = std::max(MIN_SUB, atoi(e));
-    if (const char* e = getenv("FIT_KS_MIN")) ks_min = std::max(2, std::min(KS, atoi(e)));
-    // a multi-node job needs k keys <= B on one slice: the slice that sets B has ks of them, all
-    // clean when the job opens a round, so ks >= kmax keeps every round's first job resolvable
-    while (ks_min < kmax) ks_min *= 2;
-    // two sets of per-round buffers (plans, candidates, bounds, job rows) by round parity
-    // (fit_engine_ctl.h): a round starts while the previous round's last tiles are still scanned
-    if (c->ecs.ensure(nc) || c->eco.ensure(nc) || c->h_ecs.ensure(nc) || c->h_eco.ensure(nc) ||
-        c->plan.ensure(2 * nc) ||
-        c->cand.ensure((size_t)2 * nc * per_comp_cand + (size_t)2 * nc * PAIR_AREA) ||
-        c->bnd.ensure((size_t)2 * nc * wcap) || c->wjob.ensure((size_t)2 * nc * wcap) ||
-        c->ectl.ensure(engine_ctl_bytes()) || c->ering.ensure(engine_ring_bytes()) ||
-        c->h_err.ensure(4))
-        return FIT_E_OOM;
-    if ((int64_t)2 * nc * per_comp_cand + (int64_t)2 * nc * PAIR_AREA > INT32_MAX)
-        return fail(FIT_E_INVAL, "candidate buffer exceeds 2^31 entries (%d components)", nc);
-    for (int i = 0; i < nc; ++i) {
-        const int k = comps[i];
-        CompState& s = c->h_ecs.p[i];
-        s.nb = s.sb = c->nb[k];
-        s.ne = s.se = c->nb[k + 1];
-        const int32_t len = s.ne - s.nb;
-        for (s.ks = KS;; s.ks /= 2) {
-            const int slices = MAX_SLICES * KS / s.ks;
-            s.sub = std::max(MIN_SUB, (len + SCAN_WAVES * slices - 1) / (SCAN_WAVES * slices));
-            s.nslice = std::max(1, (len + SCAN_WAVES * s.sub - 1) / (SCAN_WAVES * s.sub));
-            if (s.sub <= sub_target || s.ks / 2 < ks_min) break;
-        }
-        s.jstart = jb[k];
-        s.jend = jb[k + 1];
-        s.cand_off = (int64_t)i * per_comp_cand;
-        s.slot0 = (int32_t)(i * wcap);
-        s.cand_alt = (int64_t)(nc + i) * per_comp_cand;
-        s.slot_alt = (int32_t)((nc + i) * wcap);
-        s.pair_off = (int32_t)(2 * nc * per_comp_cand + (int64_t)2 * i * PAIR_AREA);
-        s.wmin = std::min(c->wmin, (int)wcap);
-        s.wmax = (int32_t)wcap;
-    }
-    // task ring: a committer publishes a round only after all tiles of the round before last are
-    // done, so at most 2 * nc * job tiles * slices tiles are outstanding; the ring must hold them
-    // all (a granule overwritten before its worker read it would be lost)
-    int32_t max_slices = 1;
-    for (int i = 0; i < nc; ++i) max_slices = std::max(max_slices, c->h_ecs.p[i].nslice);
-    // (+ one tile: a round's first tile may be scanned as twice the slices, K_T0PAIR)
-    if ((int64_t)2 * ring_comps(nc) * ((wcap + SCAN_JOBS - 1) / SCAN_JOBS + 1) * max_slices >
-        (int64_t)engine_ring_tasks())
-        return fail(FIT_E_INVAL, "task ring too small: %d components x %lld tiles x %d slices",
-                    nc, (long long)((wcap + SCAN_JOBS - 1) / SCAN_JOBS), max_slices);
-    size_t lds = engine_lds_bytes(maxnodes);
-    // experiment knob: a larger LDS request caps the blocks per CU (e.g. > 80 KB: one per CU)
-    if (const char* e = getenv("FIT_ENGINE_LDS_MIN")) lds = std::max(lds, (size_t)atol(e));
-    int per_cu = engine_blocks_per_cu(lds);
-    if (per_cu <= 0) return fail(FIT_E_HIP, "k_engine does not fit on a CU (lds %zu)", lds);
-    // Only the committers (blocks [0, nc), dispatched first) must be co-resident: a worker block
-    // that is not yet resident has claimed no task, so nobody waits on it.  One block per CU:
-    // the scan workers are mostly idle already, and a second block on a committer's CU slows
-    // the serial commit chain (measured: 2/CU → commit +3%, no scan gain).
-    int workers = std::max(8, std::max(1, per_cu - 1) * c->cus - nc);
-    if (const char* e = getenv("FIT_WORKERS")) workers = std::max(1, atoi(e));
-    if (c->ebusy.ensure(2 * workers) || c->h_ebusy.ensure(2 * workers) || c->h_trip.ensure(1) ||
-        c->rec_bak.ensure(std::max(c->nn, 1)))
-        return FIT_E_OOM;
-    HIP_TRY(hipMemcpyAsync(c->ecs.p, c->h_ecs.p, sizeof(CompState) * nc, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->ectl.p, 0, engine_ctl_bytes(), st));
-    HIP_TRY(hipMemsetAsync(c->ering.p, 0, engine_ring_bytes(), st));
-    // every bound KEY_INF: a round resets only the bounds its buffer set's last round used
-    HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * 2 * nc * wcap, st));
-    // the node rows as they were: a trip leaves them partly committed, and the context must stay
-    // usable after FIT_E_HIP (restored below)
-    static const bool no_backup = getenv("FIT_REC_BACKUP") && atoi(getenv("FIT_REC_BACKUP")) == 0;  // A/B only
-    if (!no_backup)
-        HIP_TRY(hipMemcpyAsync(c->rec_bak.p, c->rec.p, sizeof(NodeRec) * c->nn, hipMemcpyDeviceToDevice, st));
-    {
-        ArbGuard arb;  // one persistent launch per device at a time (see DevArb)
-        int rc = arb.take(c->device);
-        if (rc) return rc;
-        S.ms_arb_wait = arb.waited_ms;
-        HIP_TRY(hipEventRecord(c->ev[0], st));
-        HIP_TRY(launch_engine(nc + workers, lds, st, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p,
-                              c->plan.p, nc, c->rec.p, c->jl.p, cpu, mem, gpu, wall, part, nk,
-                              c->cand.p, c->bnd.p, c->wjob.p, out, kmax, c->ebusy.p, c->jpk.p,
-                              c->wd_ticks));
-        HIP_TRY(hipEventRecord(c->ev[1], st));
-        HIP_TRY(hipMemcpyAsync(c->h_eco.p, c->eco.p, sizeof(CompOut) * nc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(c->h_ebusy.p, c->ebusy.p, sizeof(int64_t) * 2 * workers,
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(c->h_err.p, c->ectl.p + engine_ctl_error_offset(), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(c->h_trip.p, c->ectl.p + engine_ctl_trip_offset(), sizeof(TripRec),
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (c->h_err.p[0]) {
-        const int rc = trip_error(c, "placement engine");
-        if (no_backup) {  // no copy was taken: the rows are partly committed, drop the table
-            c->have_nodes = c->have_tl = false;
-            return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(c->rec.p, c->rec_bak.p, sizeof(NodeRec) * c->nn, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return rc;
-    }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    S.ms_device += ms;
-    int64_t busy = 0;
-    // per worker {busy ticks, evaluations scanned}: tiles of a finished round are dropped, so
-    // the performed evaluations are counted where they happen
-    for (int i = 0; i < workers; ++i) {
-        busy += c->h_ebusy.p[2 * i];
-        S.evals += c->h_ebusy.p[2 * i + 1];
-    }
-    S.ms_scan += busy / 1e5 / workers;  // average worker busy time (100 MHz ticks)
+    E.nc = (int)E.comps.size();
+    E.wcap = std::min(c->wmax, 8192);
+    return E;
+}
+
+// One CompOut per launch component into the placement's stats; every component must have
+// resolved all its jobs.
+int fold_comp_out(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector<int>& comps, fit_stats& S) {
     double commit_max = 0;
-    for (int i = 0; i < nc; ++i) {
+    for (size_t i = 0; i < comps.size(); ++i) {
         const CompOut& o = c->h_eco.p[i];
         const int k = comps[i];
         if (o.done_jobs != jb[k + 1] - jb[k])
@@ -802,6 +562,170 @@ int run_persistent(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector
     }
     S.ms_commit += commit_max;
     return 0;
+}
+
+// The launch's buffers, its CompState rows and the task-ring check.  `keys`: candidate entries per
+// job (block-slices x keys per slice); slice(len, s) sets s.ks, s.sub and s.nslice for a component
+// of len nodes.
+template <class Slice>
+int engine_plan(fit_ctx* c, const std::vector<int32_t>& jb, const EngineComps& E, int64_t keys, Slice slice) {
+    const int nc = E.nc;
+    const int64_t wcap = E.wcap, per_comp_cand = wcap * keys;
+    // two sets of per-round buffers (plans, candidates, bounds, job rows) by round parity
+    // (fit_engine_ctl.h): a round starts while the previous round's last tiles are still scanned
+    if (c->ecs.ensure(nc) || c->eco.ensure(nc) || c->h_ecs.ensure(nc) || c->h_eco.ensure(nc) ||
+        c->plan.ensure(2 * nc) ||
+        c->cand.ensure((size_t)2 * nc * per_comp_cand + (size_t)2 * nc * PAIR_AREA) ||
+        c->bnd.ensure((size_t)2 * nc * wcap) || c->wjob.ensure((size_t)2 * nc * wcap) ||
+        c->ectl.ensure(engine_ctl_bytes()) || c->ering.ensure(engine_ring_bytes()) ||
+        c->h_err.ensure(4))
+        return FIT_E_OOM;
+    if ((int64_t)2 * nc * per_comp_cand + (int64_t)2 * nc * PAIR_AREA > INT32_MAX)
+        return fail(FIT_E_INVAL, "candidate buffer exceeds 2^31 entries (%d components)", nc);
+    int32_t max_slices = 1;
+    for (int i = 0; i < nc; ++i) {
+        const int k = E.comps[i];
+        CompState& s = c->h_ecs.p[i];
+        s.nb = s.sb = c->nb[k];
+        s.ne = s.se = c->nb[k + 1];
+        slice(s.ne - s.nb, s);
+        max_slices = std::max(max_slices, s.nslice);
+        s.jstart = jb[k];
+        s.jend = jb[k + 1];
+        s.cand_off = (int64_t)i * per_comp_cand;
+        s.slot0 = (int32_t)(i * wcap);
+        s.cand_alt = (int64_t)(nc + i) * per_comp_cand;
+        s.slot_alt = (int32_t)((nc + i) * wcap);
+        s.pair_off = (int32_t)(2 * nc * per_comp_cand + (int64_t)2 * i * PAIR_AREA);
+        s.wmin = std::min(c->wmin, (int)wcap);
+        s.wmax = (int32_t)wcap;
+    }
+    // task ring: a committer publishes a round only after all tiles of the round before last are
+    // done, so at most 2 * nc * job tiles * slices tiles are outstanding; the ring must hold them
+    // all (a granule overwritten before its worker read it would be lost)
+    // (+ one tile: a round's first tile may be scanned as twice the slices, K_T0PAIR / TL_T0PAIR)
+    if ((int64_t)2 * ring_comps(nc) * ((wcap + SCAN_JOBS - 1) / SCAN_JOBS + 1) * max_slices >
+        (int64_t)engine_ring_tasks())
+        return fail(FIT_E_INVAL, "task ring too small: %d components x %lld tiles x %d slices",
+                    nc, (long long)((wcap + SCAN_JOBS - 1) / SCAN_JOBS), max_slices);
+    return 0;
+}
+
+// The launch itself: CompState upload and the control-block, ring and bound resets, then, under
+// the device lock (one persistent launch per device at a time, see DevArb) from before the launch
+// to the synchronisation that ends it, launch() between two events and the read-back of CompOut,
+// the workers' counters, the error word and the first trip record.  settle(trip_rc) recovers: it
+// gets the trip's error code (0: no trip) and returns the call's.  Then the stats.
+template <class Launch, class Settle>
+int engine_launch(fit_ctx* c, const std::vector<int32_t>& jb, const EngineComps& E, int workers,
+                  const char* name, Launch launch, Settle settle, fit_stats& S) {
+    const int nc = E.nc;
+    hipStream_t st = c->st;
+    if (c->ebusy.ensure(2 * workers) || c->h_ebusy.ensure(2 * workers) || c->h_trip.ensure(1))
+        return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->ecs.p, c->h_ecs.p, sizeof(CompState) * nc, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c->ectl.p, 0, engine_ctl_bytes(), st));
+    HIP_TRY(hipMemsetAsync(c->ering.p, 0, engine_ring_bytes(), st));
+    // every bound KEY_INF: a round resets only the bounds its buffer set's last round used
+    HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * 2 * nc * E.wcap, st));
+    {
+        ArbGuard arb;
+        int rc = arb.take(c->device);
+        if (rc) return rc;
+        S.ms_arb_wait = arb.waited_ms;
+        HIP_TRY(hipEventRecord(c->ev[0], st));
+        rc = launch();
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(c->ev[1], st));
+        HIP_TRY(hipMemcpyAsync(c->h_eco.p, c->eco.p, sizeof(CompOut) * nc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->h_ebusy.p, c->ebusy.p, sizeof(int64_t) * 2 * workers,
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->h_err.p, c->ectl.p + engine_ctl_error_offset(), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->h_trip.p, c->ectl.p + engine_ctl_trip_offset(), sizeof(TripRec),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (int rc = settle(c->h_err.p[0] ? trip_error(c, name) : 0)) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    S.ms_device += ms;
+    int64_t busy = 0;
+    // per worker {busy ticks, evaluations scanned}: tiles of a finished round are dropped, so
+    // the performed evaluations are counted where they happen
+    for (int i = 0; i < workers; ++i) {
+        busy += c->h_ebusy.p[2 * i];
+        S.evals += c->h_ebusy.p[2 * i + 1];
+    }
+    S.ms_scan += busy / 1e5 / workers;  // average worker busy time (100 MHz ticks)
+    return fold_comp_out(c, jb, E.comps, S);
+}
+
+// All rounds of all owned components in one launch (fit_persistent.hip, DESIGN.md §3.6).
+int run_persistent(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector<char>& owned,
+                   const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* wall,
+                   const uint16_t* part, const uint16_t* nk, int32_t* out, int32_t kmax,
+                   fit_stats& S) {
+    hipStream_t st = c->st;
+    const EngineComps E = engine_comps(c, jb, owned);
+    const int nc = E.nc;
+    if (nc == 0) return 0;
+    // keys per block-slice: KS, halved (slices doubled, the same MAX_SLICES * KS candidates per
+    // job) while a wave's sub-slice would exceed sub_target nodes — a round's first job tile, which
+    // the commit waits for, then spreads over more blocks.  C3o (one 100k-node component): KS 16
+    // 552 ms, 8 471 ms, 4 441 ms, 2 480 ms (the bound B, a minimum over more slices of fewer keys,
+    // turns tight: 891 rescans); C3 / C2 components stay at KS (sub-slices of 98 / 64 nodes).
+    int sub_target = 256, ks_min = 4;
+    if (const char* e = getenv("FIT_SUB_TARGET")) sub_target = std::max(MIN_SUB, atoi(e));
+    if (const char* e = getenv("FIT_KS_MIN")) ks_min = std::max(2, std::min(KS, atoi(e)));
+    // a multi-node job needs k keys <= B on one slice: the slice that sets B has ks of them, all
+    // clean when the job opens a round, so ks >= kmax keeps every round's first job resolvable
+    while (ks_min < kmax) ks_min *= 2;
+    int rc = engine_plan(c, jb, E, (int64_t)MAX_SLICES * KS, [&](int32_t len, CompState& s) {
+        for (s.ks = KS;; s.ks /= 2) {
+            const int slices = MAX_SLICES * KS / s.ks;
+            s.sub = std::max(MIN_SUB, (len + SCAN_WAVES * slices - 1) / (SCAN_WAVES * slices));
+            s.nslice = std::max(1, (len + SCAN_WAVES * s.sub - 1) / (SCAN_WAVES * s.sub));
+            if (s.sub <= sub_target || s.ks / 2 < ks_min) break;
+        }
+    });
+    if (rc) return rc;
+    size_t lds = engine_lds_bytes(E.maxnodes);
+    // experiment knob: a larger LDS request caps the blocks per CU (e.g. > 80 KB: one per CU)
+    if (const char* e = getenv("FIT_ENGINE_LDS_MIN")) lds = std::max(lds, (size_t)atol(e));
+    int per_cu = engine_blocks_per_cu(lds);
+    if (per_cu <= 0) return fail(FIT_E_HIP, "k_engine does not fit on a CU (lds %zu)", lds);
+    // Only the committers (blocks [0, nc), dispatched first) must be co-resident: a worker block
+    // that is not yet resident has claimed no task, so nobody waits on it.  One block per CU:
+    // the scan workers are mostly idle already, and a second block on a committer's CU slows
+    // the serial commit chain (measured: 2/CU → commit +3%, no scan gain).
+    int workers = std::max(8, std::max(1, per_cu - 1) * c->cus - nc);
+    if (const char* e = getenv("FIT_WORKERS")) workers = std::max(1, atoi(e));
+    // the node rows as they were: a trip leaves them partly committed, and the context must stay
+    // usable after FIT_E_HIP (restored below)
+    static const bool no_backup = getenv("FIT_REC_BACKUP") && atoi(getenv("FIT_REC_BACKUP")) == 0;  // A/B only
+    if (c->rec_bak.ensure(std::max(c->nn, 1))) return FIT_E_OOM;
+    if (!no_backup)
+        HIP_TRY(hipMemcpyAsync(c->rec_bak.p, c->rec.p, sizeof(NodeRec) * c->nn, hipMemcpyDeviceToDevice, st));
+    return engine_launch(
+        c, jb, E, workers, "placement engine",
+        [&]() -> int {
+            HIP_TRY(launch_engine(nc + workers, lds, st, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p,
+                                  c->plan.p, nc, c->rec.p, c->jl.p, cpu, mem, gpu, wall, part, nk,
+                                  c->cand.p, c->bnd.p, c->wjob.p, out, kmax, c->ebusy.p, c->jpk.p,
+                                  c->wd_ticks));
+            return 0;
+        },
+        [&](int trip) -> int {
+            if (!trip) return 0;
+            if (no_backup) {  // no copy was taken: the rows are partly committed, drop the table
+                c->have_nodes = c->have_tl = false;
+                return trip;
+            }
+            HIP_TRY(hipMemcpyAsync(c->rec.p, c->rec_bak.p, sizeof(NodeRec) * c->nn, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return trip;
+        },
+        S);
 }
 
 // The demand-class engine (fit_class.hip): one workgroup per component, no
@@ -855,6 +779,31 @@ int run_class(fit_ctx* c, int32_t J, const std::vector<int32_t>& jb, const std::
     return 0;
 }
 
+// The demand classes of every component's jobs (k_classify, fit_class.hip), enqueued; the class
+// counts are in h_cls_n after the next synchronisation, for classes_fit.
+int enqueue_classify(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                     const uint16_t* part) {
+    const int C = c->ncomp;
+    hipStream_t st = c->st;
+    const size_t ts = (size_t)C * class_table_slots() * class_slot_bytes();
+    if (c->jcls.ensure(std::max(J, 1)) || c->cls_tab.ensure(ts) || c->cls_dem.ensure((size_t)C * class_max()) ||
+        c->cls_n.ensure(C) || c->h_cls_n.ensure(C))
+        return FIT_E_OOM;
+    HIP_TRY(hipMemsetAsync(c->cls_tab.p, 0, ts, st));
+    HIP_TRY(hipMemsetAsync(c->cls_n.p, 0, sizeof(int32_t) * C, st));
+    HIP_TRY(launch_classify(st, c->jcomp.p, cpu, mem, gpu, part, J, c->cls_tab.p, c->cls_dem.p, c->cls_n.p,
+                            c->jcls.p));
+    HIP_TRY(hipMemcpyAsync(c->h_cls_n.p, c->cls_n.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// whether every component has at most class_max() demand classes
+bool classes_fit(const fit_ctx* c) {
+    for (int k = 0; k < c->ncomp; ++k)
+        if (c->h_cls_n.p[k] > class_max()) return false;
+    return true;
+}
+
 // Per-component job lists in priority order (stable), built on the device from the prefilter's
 // component ids (launch_joblists: counting sort by component); only the component offsets and
 // two counters come back to the host.  jb[k] .. jb[k+1] = component k's list range.
@@ -877,23 +826,12 @@ int build_job_lists(fit_ctx* c, int32_t J, fit_stats& S, std::vector<int32_t>& j
     // the counters, the component offsets and the multi-node offsets (mbd[C]: multi-node jobs)
     HIP_TRY(hipMemcpyAsync(c->h_jls.p, g, sizeof(int32_t) * (2 * (C + 1) + 2), hipMemcpyDeviceToHost, st));
     if (classify) {
-        const size_t ts = (size_t)C * class_table_slots() * class_slot_bytes();
-        if (c->jcls.ensure(std::max(J, 1)) || c->cls_tab.ensure(ts) ||
-            c->cls_dem.ensure((size_t)C * class_max()) || c->cls_n.ensure(C) || c->h_cls_n.ensure(C))
-            return FIT_E_OOM;
-        HIP_TRY(hipMemsetAsync(c->cls_tab.p, 0, ts, st));
-        HIP_TRY(hipMemsetAsync(c->cls_n.p, 0, sizeof(int32_t) * C, st));
-        HIP_TRY(launch_classify(st, c->jcomp.p, cpu, mem, gpu, part, J, c->cls_tab.p, c->cls_dem.p, c->cls_n.p,
-                                c->jcls.p));
-        HIP_TRY(hipMemcpyAsync(c->h_cls_n.p, c->cls_n.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
+        const int rc = enqueue_classify(c, J, cpu, mem, gpu, part);
+        if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (c->h_jls.p[1]) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > kmax");
-    if (cls_ok) {
-        *cls_ok = classify;
-        for (int k = 0; classify && k < C; ++k)
-            if (c->h_cls_n.p[k] > class_max()) *cls_ok = false;
-    }
+    if (cls_ok) *cls_ok = classify && classes_fit(c);
     S.rejected = c->h_jls.p[0];
     jb.assign(c->h_jls.p + 2, c->h_jls.p + 2 + C + 1);
     c->last_multi = c->h_jls.p[2 + C + 1 + C];
@@ -905,21 +843,10 @@ int build_job_lists(fit_ctx* c, int32_t J, fit_stats& S, std::vector<int32_t>& j
 // the multi-node jobs the automatic choice needs): k_classify and one synchronisation.
 int classify_jobs(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                   const uint16_t* part, bool* cls_ok) {
-    const int C = c->ncomp;
-    hipStream_t st = c->st;
-    const size_t ts = (size_t)C * class_table_slots() * class_slot_bytes();
-    if (c->jcls.ensure(std::max(J, 1)) || c->cls_tab.ensure(ts) || c->cls_dem.ensure((size_t)C * class_max()) ||
-        c->cls_n.ensure(C) || c->h_cls_n.ensure(C))
-        return FIT_E_OOM;
-    HIP_TRY(hipMemsetAsync(c->cls_tab.p, 0, ts, st));
-    HIP_TRY(hipMemsetAsync(c->cls_n.p, 0, sizeof(int32_t) * C, st));
-    HIP_TRY(launch_classify(st, c->jcomp.p, cpu, mem, gpu, part, J, c->cls_tab.p, c->cls_dem.p, c->cls_n.p,
-                            c->jcls.p));
-    HIP_TRY(hipMemcpyAsync(c->h_cls_n.p, c->cls_n.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *cls_ok = true;
-    for (int k = 0; k < C; ++k)
-        if (c->h_cls_n.p[k] > class_max()) *cls_ok = false;
+    const int rc = enqueue_classify(c, J, cpu, mem, gpu, part);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->st));
+    *cls_ok = classes_fit(c);
     return 0;
 }
 
@@ -975,6 +902,102 @@ int place_direct(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, 
     S.rounds = C > 0 && J > S.rejected ? 1 : 0;
     S.components = C;
     S.engine = 2;
+    return 0;
+}
+
+// The host-driven speculative rounds, shared by the plain fit and the backfill:
+// per round the plans of every component's window, scan(blocks, this rank's candidate section),
+// the exchange when the nodes are sharded over ranks, commit(entries per lane, largest component
+// with a window, candidates per rank, ranks) and the windows' update from the results.  `keys`
+// per (job, block-slice), at most `slices` block-slices per job per rank of >= min_sub nodes per
+// wave; only `owned` components get a window.
+template <class Scan, class Commit>
+int run_rounds(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector<char>& owned, bool node_sharded,
+               int keys, int slices, int min_sub, Scan scan, Commit commit, fit_stats& S) {
+    const int C = c->ncomp;
+    hipStream_t st = c->st;
+    const int shards = node_sharded ? c->world : 1;
+    const int srank = node_sharded ? c->rank : 0;
+    std::vector<int32_t> cur(jb.begin(), jb.end() - 1), win(C, c->wmin);
+    if (c->plan.ensure(C + 1) || c->res.ensure(C + 1) || c->h_plan.ensure(C + 1) ||
+        c->h_res.ensure(C + 1))
+        return FIT_E_OOM;
+    float ms;
+    for (;;) {
+        int64_t blocks = 0, slots = 0, cand_n = 0, evals = 0;
+        int epl = 1;
+        int32_t maxlen = 0;
+        for (int k = 0; k < C; ++k) {
+            CompPlan& P = c->h_plan.p[k];
+            memset(&P, 0, sizeof P);
+            P.nb = c->nb[k];
+            P.ne = c->nb[k + 1];
+            const int32_t len = P.ne - P.nb;
+            const int32_t per = (len + shards - 1) / shards;
+            P.sb = std::min(P.ne, P.nb + per * srank);
+            P.se = std::min(P.ne, P.sb + per);
+            P.ks = keys;
+            P.sub = std::max(min_sub, (per + SCAN_WAVES * slices - 1) / (SCAN_WAVES * slices));
+            P.nslice = std::max(1, (per + SCAN_WAVES * P.sub - 1) / (SCAN_WAVES * P.sub));
+            epl = std::max(epl, (shards * P.nslice * keys + 63) / 64);
+            P.jbase = cur[k];
+            P.w = owned[k] ? std::min(win[k], jb[k + 1] - cur[k]) : 0;
+            P.blk0 = (int32_t)blocks;
+            P.cand_off = cand_n;
+            P.slot0 = (int32_t)slots;
+            if (P.w > 0) {
+                blocks += (int64_t)((P.w + SCAN_JOBS - 1) / SCAN_JOBS) * P.nslice;
+                cand_n += (int64_t)P.w * P.nslice * keys;
+                slots += P.w;
+                evals += (int64_t)P.w * (P.se - P.sb);
+                maxlen = std::max(maxlen, len);
+            }
+        }
+        if (slots == 0) break;
+        S.rounds++;
+        S.evals += evals;
+        if (c->cand.ensure((size_t)cand_n * shards) || c->bnd.ensure(slots) ||
+            c->wjob.ensure(slots))
+            return FIT_E_OOM;
+        HIP_TRY(hipMemcpyAsync(c->plan.p, c->h_plan.p, sizeof(CompPlan) * C, hipMemcpyHostToDevice,
+                               st));
+        HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * slots, st));
+        HIP_TRY(hipEventRecord(c->ev[0], st));
+        HIP_TRY(scan((int)blocks, c->cand.p + (size_t)srank * cand_n));
+        HIP_TRY(hipEventRecord(c->ev[1], st));
+        if (node_sharded) {
+            // every rank scanned its node shard: gather all candidate sections, min the bounds
+            int rc = xchg(c, FIT_XCHG_ALLGATHER_U64, c->cand.p, cand_n);
+            if (!rc) rc = xchg(c, FIT_XCHG_MIN_U64, c->bnd.p, slots);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipEventRecord(c->ev[2], st));
+        HIP_TRY(commit(epl, maxlen, cand_n, shards));
+        HIP_TRY(hipEventRecord(c->ev[3], st));
+        HIP_TRY(hipMemcpyAsync(c->h_res.p, c->res.p, sizeof(CommitResult) * C,
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        S.ms_scan += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
+        S.ms_exchange += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        S.ms_commit += ms;
+        for (int k = 0; k < C; ++k) {
+            const CompPlan& P = c->h_plan.p[k];
+            if (P.w == 0) continue;
+            const CommitResult& R = c->h_res.p[k];
+            if (R.done < 0 || R.done > P.w)
+                return fail(FIT_E_HIP, "commit returned %d of window %d", R.done, P.w);
+            cur[k] += R.done;
+            S.placed += R.placed;
+            if (R.stop == 1) S.stops_rescan++;
+            if (R.stop == 2) S.stops_dirty++;
+            const int32_t nw = R.stop ? 2 * R.done : 2 * P.w;
+            win[k] = std::max(c->wmin, std::min(c->wmax, nw));
+        }
+    }
+    S.ms_device = S.ms_scan + S.ms_exchange + S.ms_commit;
     return 0;
 }
 
@@ -1048,8 +1071,6 @@ int place_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, co
     S.shard_mode = mode;
     S.components = C;
     const bool node_sharded = mode == FIT_SHARD_NODES;
-    const int shards = node_sharded ? c->world : 1;
-    const int srank = node_sharded ? c->rank : 0;
 
     // 3. speculative rounds: one persistent launch, or the host-driven loop (node sharding
     // exchanges candidates over RCCL every round, so it keeps the host loop; a small batch is
@@ -1063,93 +1084,19 @@ int place_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, co
         if (rc) return rc;
         S.engine = 1;
     } else {
-    std::vector<int32_t> cur(jb.begin(), jb.end() - 1), win(C, c->wmin);
-    if (c->plan.ensure(C + 1) || c->res.ensure(C + 1) || c->h_plan.ensure(C + 1) ||
-        c->h_res.ensure(C + 1))
-        return FIT_E_OOM;
-    float ms;
-    for (;;) {
-        int64_t blocks = 0, slots = 0, cand_n = 0, evals = 0;
-        int epl = 1;
-        size_t lds = 0;
-        bool any = false;
-        for (int k = 0; k < C; ++k) {
-            CompPlan& P = c->h_plan.p[k];
-            P.k0 = 0;
-            memset(&P, 0, sizeof P);
-            P.nb = c->nb[k];
-            P.ne = c->nb[k + 1];
-            const int32_t len = P.ne - P.nb;
-            const int32_t per = (len + shards - 1) / shards;
-            P.sb = std::min(P.ne, P.nb + per * srank);
-            P.se = std::min(P.ne, P.sb + per);
-            // sub-slices of >= MIN_SUB nodes, at most MAX_SLICES block-slices per job per rank
-            P.ks = KS;
-            P.sub = std::max(MIN_SUB, (per + SCAN_WAVES * MAX_SLICES - 1) / (SCAN_WAVES * MAX_SLICES));
-            P.nslice = std::max(1, (per + SCAN_WAVES * P.sub - 1) / (SCAN_WAVES * P.sub));
-            epl = std::max(epl, (shards * P.nslice * KS + 63) / 64);
-            P.jbase = cur[k];
-            P.w = owned[k] ? std::min(win[k], jb[k + 1] - cur[k]) : 0;
-            P.blk0 = (int32_t)blocks;
-            P.cand_off = cand_n;
-            P.slot0 = (int32_t)slots;
-            if (P.w > 0) {
-                any = true;
-                blocks += (int64_t)((P.w + SCAN_JOBS - 1) / SCAN_JOBS) * P.nslice;
-                cand_n += (int64_t)P.w * P.nslice * KS;
-                slots += P.w;
-                evals += (int64_t)P.w * (P.se - P.sb);
-                lds = std::max(lds, (size_t)((len + 31) / 32) * 4);
-            }
-        }
-        if (!any) break;
-        S.rounds++;
-        S.evals += evals;
-        if (c->cand.ensure((size_t)cand_n * shards) || c->bnd.ensure(slots) ||
-            c->wjob.ensure(slots))
-            return FIT_E_OOM;
-        HIP_TRY(hipMemcpyAsync(c->plan.p, c->h_plan.p, sizeof(CompPlan) * C, hipMemcpyHostToDevice,
-                               st));
-        HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * slots, st));
-        HIP_TRY(hipEventRecord(c->ev[0], st));
-        HIP_TRY(launch_scan((int)blocks, st, c->rec.p, c->jl.p, cpu, mem, gpu, wall, part, nk,
-                            c->plan.p, C, c->cand.p + (size_t)srank * cand_n, c->bnd.p,
-                            c->wjob.p));
-        HIP_TRY(hipEventRecord(c->ev[1], st));
-        if (node_sharded) {
-            // every rank scanned its node shard: gather all candidate sections, min the bounds
-            int rc = xchg(c, FIT_XCHG_ALLGATHER_U64, c->cand.p, cand_n);
-            if (!rc) rc = xchg(c, FIT_XCHG_MIN_U64, c->bnd.p, slots);
-            if (rc) return rc;
-        }
-        HIP_TRY(hipEventRecord(c->ev[2], st));
-        HIP_TRY(launch_commit(C, epl, lds, st, c->rec.p, c->plan.p, c->cand.p, cand_n, shards,
-                              c->bnd.p, c->wjob.p, out, kmax, c->res.p));
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-        HIP_TRY(hipMemcpyAsync(c->h_res.p, c->res.p, sizeof(CommitResult) * C,
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        S.ms_scan += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
-        S.ms_exchange += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        S.ms_commit += ms;
-        for (int k = 0; k < C; ++k) {
-            const CompPlan& P = c->h_plan.p[k];
-            if (P.w == 0) continue;
-            const CommitResult& R = c->h_res.p[k];
-            if (R.done < 0 || R.done > P.w)
-                return fail(FIT_E_HIP, "commit returned %d of window %d", R.done, P.w);
-            cur[k] += R.done;
-            S.placed += R.placed;
-            if (R.stop == 1) S.stops_rescan++;
-            if (R.stop == 2) S.stops_dirty++;
-            int32_t nw = R.stop ? 2 * R.done : 2 * P.w;
-            win[k] = std::max(c->wmin, std::min(c->wmax, nw));
-        }
-    }
-    S.ms_device = S.ms_scan + S.ms_exchange + S.ms_commit;
+        int rc = run_rounds(
+            c, jb, owned, node_sharded, KS, MAX_SLICES, MIN_SUB,
+            [&](int blocks, uint64_t* cand) {
+                return launch_scan(blocks, st, c->rec.p, c->jl.p, cpu, mem, gpu, wall, part, nk, c->plan.p, C,
+                                   cand, c->bnd.p, c->wjob.p);
+            },
+            // the commit's dirty bitmap in LDS covers the largest component that has a window
+            [&](int epl, int32_t maxlen, int64_t cand_n, int shards) {
+                return launch_commit(C, epl, (size_t)((maxlen + 31) / 32) * 4, st, c->rec.p, c->plan.p,
+                                     c->cand.p, cand_n, shards, c->bnd.p, c->wjob.p, out, kmax, c->res.p);
+            },
+            S);
+        if (rc) return rc;
     }  // host-driven rounds
     if (mode == FIT_SHARD_COMPONENTS) {
         // each rank placed only its components: combine placements (owner's >= -1 beats -1;
@@ -1186,64 +1133,23 @@ int place_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, co
 int run_persistent_tl(fit_ctx* c, const std::vector<int32_t>& jb, const int32_t* cpu,
                       const int32_t* mem, const int32_t* gpu, const int32_t* wall,
                       const uint16_t* part, int32_t* out, int32_t* outs, fit_stats& S) {
-    const int C = c->ncomp;
     hipStream_t st = c->st;
-    std::vector<int> comps;
-    int32_t maxnodes = 0;
-    for (int k = 0; k < C; ++k)
-        if (jb[k + 1] > jb[k]) {
-            comps.push_back(k);
-            maxnodes = std::max(maxnodes, c->nb[k + 1] - c->nb[k]);
-        }
-    const int nc = (int)comps.size();
+    const EngineComps E = engine_comps(c, jb, std::vector<char>(c->ncomp, 1));
+    const int nc = E.nc;
     if (nc == 0) return 0;
-    const int R = engine_tl_runs(maxnodes);
+    const int R = engine_tl_runs(E.maxnodes);
     if (R < 1) return fail(FIT_E_INVAL, "partition component of %d nodes is too large for the "
-                                        "timeline engine's LDS", maxnodes);
-    const int64_t wcap = std::min(c->wmax, 8192);
+                                        "timeline engine's LDS", E.maxnodes);
     int slices = TL_SLICES, tl_min_sub = TL_MIN_SUB;
     if (const char* e = getenv("FIT_TL_SLICES")) slices = std::max(1, std::min(atoi(e), TL_SLICES));
     if (const char* e = getenv("FIT_TL_MINSUB")) tl_min_sub = std::max(1, atoi(e));
-    const int64_t per_comp_cand = wcap * slices * TL_KS;
-    // two sets of per-round buffers by round parity (see run_persistent)
-    if (c->ecs.ensure(nc) || c->eco.ensure(nc) || c->h_ecs.ensure(nc) || c->h_eco.ensure(nc) ||
-        c->plan.ensure(2 * nc) ||
-        c->cand.ensure((size_t)2 * nc * per_comp_cand + (size_t)2 * nc * PAIR_AREA) ||
-        c->bnd.ensure((size_t)2 * nc * wcap) || c->wjob.ensure((size_t)2 * nc * wcap) ||
-        c->ectl.ensure(engine_ctl_bytes()) || c->ering.ensure(engine_ring_bytes()) ||
-        c->h_err.ensure(4))
-        return FIT_E_OOM;
-    if ((int64_t)2 * nc * per_comp_cand + (int64_t)2 * nc * PAIR_AREA > INT32_MAX)
-        return fail(FIT_E_INVAL, "candidate buffer exceeds 2^31 entries (%d components)", nc);
-    for (int i = 0; i < nc; ++i) {
-        const int k = comps[i];
-        CompState& s = c->h_ecs.p[i];
-        s.nb = s.sb = c->nb[k];
-        s.ne = s.se = c->nb[k + 1];
-        const int32_t len = s.ne - s.nb;
+    int rc = engine_plan(c, jb, E, (int64_t)slices * TL_KS, [&](int32_t len, CompState& s) {
         s.ks = TL_KS;
         s.sub = std::max(tl_min_sub, (len + SCAN_WAVES * slices - 1) / (SCAN_WAVES * slices));
         s.nslice = std::max(1, (len + SCAN_WAVES * s.sub - 1) / (SCAN_WAVES * s.sub));
-        s.jstart = jb[k];
-        s.jend = jb[k + 1];
-        s.cand_off = (int64_t)i * per_comp_cand;
-        s.slot0 = (int32_t)(i * wcap);
-        s.cand_alt = (int64_t)(nc + i) * per_comp_cand;
-        s.slot_alt = (int32_t)((nc + i) * wcap);
-        s.pair_off = (int32_t)(2 * nc * per_comp_cand + (int64_t)2 * i * PAIR_AREA);
-        s.wmin = std::min(c->wmin, (int)wcap);
-        s.wmax = (int32_t)wcap;
-    }
-    {  // task ring capacity (see run_persistent)
-        int32_t max_slices = 1;
-        for (int i = 0; i < nc; ++i) max_slices = std::max(max_slices, c->h_ecs.p[i].nslice);
-        // (+ one tile: a round's first tile may be scanned as twice the slices, TL_T0PAIR)
-        if ((int64_t)2 * ring_comps(nc) * ((wcap + SCAN_JOBS - 1) / SCAN_JOBS + 1) * max_slices >
-            (int64_t)engine_ring_tasks())
-            return fail(FIT_E_INVAL, "task ring too small: %d components x %lld tiles x %d slices",
-                        nc, (long long)((wcap + SCAN_JOBS - 1) / SCAN_JOBS), max_slices);
-    }
-    const size_t lds = engine_tl_lds_bytes(maxnodes);
+    });
+    if (rc) return rc;
+    const size_t lds = engine_tl_lds_bytes(E.maxnodes);
     // FIT_TL_SPLIT: committers and scan workers as two concurrent launches (fit_timeline.hip
     // k_engine_tl_t): the workers' launch carries only the scan's registers and LDS, so several
     // worker blocks share a CU instead of one block per CU for everything
@@ -1262,94 +1168,50 @@ int run_persistent_tl(fit_ctx* c, const std::vector<int32_t>& jb, const int32_t*
             hipHostMalloc(&c->resident, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
             return fail(FIT_E_HIP, "split launch: stream / event / mapped flag");
     }
-    if (c->ebusy.ensure(2 * workers) || c->h_ebusy.ensure(2 * workers) || c->h_trip.ensure(1))
-        return FIT_E_OOM;
-    HIP_TRY(hipMemcpyAsync(c->ecs.p, c->h_ecs.p, sizeof(CompState) * nc, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->ectl.p, 0, engine_ctl_bytes(), st));
-    HIP_TRY(hipMemsetAsync(c->ering.p, 0, engine_ring_bytes(), st));
-    // every bound KEY_INF: a round resets only the bounds its buffer set's last round used
-    HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * 2 * nc * wcap, st));
-    ArbGuard arb;  // one persistent launch per device at a time (see DevArb); to the sync below
-    {
-        int rc = arb.take(c->device);
-        if (rc) return rc;
-        S.ms_arb_wait = arb.waited_ms;
-    }
-    HIP_TRY(hipEventRecord(c->ev[0], st));
+    // mode 0: committers and workers in one grid; 1: the committers; 2: the workers
+    auto launch = [&](int blocks, size_t l, hipStream_t s, int mode, unsigned* dres) {
+        return launch_engine_tl(blocks, l, s, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p, c->plan.p, nc,
+                                c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem, gpu, wall, part, c->cand.p,
+                                c->bnd.p, c->wjob.p, c->perm.p, out, outs, c->tl_slots, c->tl_slot_min, R,
+                                c->ebusy.p, mode, dres, c->wd_ticks);
+    };
     bool resident_late = false;
-    if (!split) {
-        HIP_TRY(launch_engine_tl(nc + workers, lds, st, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p,
-                                 c->plan.p, nc, c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem, gpu, wall,
-                                 part, c->cand.p, c->bnd.p, c->wjob.p, c->perm.p, out, outs,
-                                 c->tl_slots, c->tl_slot_min, R, c->ebusy.p, 0, nullptr, c->wd_ticks));
-    } else {
-        __atomic_store_n(c->resident, 0u, __ATOMIC_RELEASE);
-        unsigned* dres = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&dres), c->resident, 0));
-        HIP_TRY(launch_engine_tl(nc, lds, st, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p, c->plan.p,
-                                 nc, c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem, gpu, wall, part,
-                                 c->cand.p, c->bnd.p, c->wjob.p, c->perm.p, out, outs, c->tl_slots,
-                                 c->tl_slot_min, R, c->ebusy.p, 1, dres, c->wd_ticks));
-        // the workers go in once every committer block holds its CU (a worker block on a CU
-        // would leave a committer no room, and the committers' rounds wait for workers)
-        const auto t0 = std::chrono::steady_clock::now();
-        while (__atomic_load_n(c->resident, __ATOMIC_ACQUIRE) < (unsigned)nc) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-                resident_late = true;  // launched anyway: the kernels' own watchdogs end it
-                break;
+    rc = engine_launch(
+        c, jb, E, workers, "timeline engine",
+        [&]() -> int {
+            if (!split) {
+                HIP_TRY(launch(nc + workers, lds, st, 0, nullptr));
+                return 0;
             }
-        }
-        HIP_TRY(hipStreamWaitEvent(c->st2, c->ev[0], 0));  // after the control-block resets
-        HIP_TRY(launch_engine_tl(workers, lds_w, c->st2, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p,
-                                 c->plan.p, nc, c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem, gpu, wall,
-                                 part, c->cand.p, c->bnd.p, c->wjob.p, c->perm.p, out, outs,
-                                 c->tl_slots, c->tl_slot_min, R, c->ebusy.p, 2, nullptr, c->wd_ticks));
-        HIP_TRY(hipEventRecord(c->ev_join, c->st2));
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-    }
-    HIP_TRY(hipEventRecord(c->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(c->h_eco.p, c->eco.p, sizeof(CompOut) * nc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(c->h_ebusy.p, c->ebusy.p, sizeof(int64_t) * 2 * workers,
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(c->h_err.p, c->ectl.p + engine_ctl_error_offset(), 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(c->h_trip.p, c->ectl.p + engine_ctl_trip_offset(), sizeof(TripRec),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // a trip leaves the run lists partly reserved: the timeline must be loaded again (a copy of
-    // the slab per placement would cost more than the rare reload); the node table is untouched
-    if (c->h_err.p[0]) {
-        c->have_tl = false;
-        return trip_error(c, "timeline engine");
-    }
-    if (resident_late) {
-        c->have_tl = false;
-        return fail(FIT_E_HIP, "timeline engine: committer blocks not resident after 10 s");
-    }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    S.ms_device += ms;
-    int64_t busy = 0;
-    // per worker {busy ticks, evaluations scanned}: tiles of a finished round are dropped, so
-    // the performed evaluations are counted where they happen
-    for (int i = 0; i < workers; ++i) {
-        busy += c->h_ebusy.p[2 * i];
-        S.evals += c->h_ebusy.p[2 * i + 1];
-    }
-    S.ms_scan += busy / 1e5 / workers;
-    double commit_max = 0;
-    for (int i = 0; i < nc; ++i) {
-        const CompOut& o = c->h_eco.p[i];
-        const int k = comps[i];
-        if (o.done_jobs != jb[k + 1] - jb[k])
-            return fail(FIT_E_HIP, "component %d resolved %lld of %d jobs", k, (long long)o.done_jobs,
-                        jb[k + 1] - jb[k]);
-        S.placed += o.placed;
-        S.rounds = std::max<int64_t>(S.rounds, o.rounds);
-        S.stops_rescan += o.stops_rescan;
-        S.stops_dirty += o.stops_dirty;
-        commit_max = std::max(commit_max, o.t_commit / 1e5);
-    }
-    S.ms_commit += commit_max;
+            __atomic_store_n(c->resident, 0u, __ATOMIC_RELEASE);
+            unsigned* dres = nullptr;
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&dres), c->resident, 0));
+            HIP_TRY(launch(nc, lds, st, 1, dres));
+            // the workers go in once every committer block holds its CU (a worker block on a CU
+            // would leave a committer no room, and the committers' rounds wait for workers)
+            const auto t0 = std::chrono::steady_clock::now();
+            while (__atomic_load_n(c->resident, __ATOMIC_ACQUIRE) < (unsigned)nc) {
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
+                    resident_late = true;  // launched anyway: the kernels' own watchdogs end it
+                    break;
+                }
+            }
+            HIP_TRY(hipStreamWaitEvent(c->st2, c->ev[0], 0));  // after the control-block resets
+            HIP_TRY(launch(workers, lds_w, c->st2, 2, nullptr));
+            HIP_TRY(hipEventRecord(c->ev_join, c->st2));
+            HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
+            return 0;
+        },
+        // a trip leaves the run lists partly reserved: the timeline must be loaded again (a copy of
+        // the slab per placement would cost more than the rare reload); the node table is untouched
+        [&](int trip) -> int {
+            if (trip || resident_late) c->have_tl = false;
+            if (trip) return trip;
+            if (resident_late) return fail(FIT_E_HIP, "timeline engine: committer blocks not resident after 10 s");
+            return 0;
+        },
+        S);
+    if (rc) return rc;
     S.engine = 1;
     return 0;
 }
@@ -1371,7 +1233,6 @@ int place_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem,
     int rc = build_job_lists(c, J, S, jb);
     if (rc) return rc;
     const bool node_sharded = c->collective();
-    const int shards = c->world, srank = c->rank;
     S.shard_mode = node_sharded ? FIT_SHARD_NODES : 0;
     S.components = C;
     if (c->persistent && !node_sharded && J - S.rejected > c->small_batch) {
@@ -1382,102 +1243,32 @@ int place_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem,
         if (stats) *stats = S;
         return 0;
     }
-    std::vector<int32_t> cur(jb.begin(), jb.end() - 1), win(C, c->wmin);
-    if (c->plan.ensure(C + 1) || c->res.ensure(C + 1) || c->h_plan.ensure(C + 1) ||
-        c->h_res.ensure(C + 1))
-        return FIT_E_OOM;
     int32_t maxlen = 1;
     for (int k = 0; k < C; ++k) maxlen = std::max(maxlen, c->nb[k + 1] - c->nb[k]);
     const size_t lds = commit_tl_lds_bytes(maxlen);
     const int runs = commit_tl_runs(maxlen);
+    const int shards = node_sharded ? c->world : 1;
+    // more, shorter block-slices than the plain fit: a run walk costs more per node, so the scan
+    // wants more waves in flight; candidate entries per job stay <= 256
     int slices = std::max(1, TL_SLICES / shards), tl_min_sub = TL_MIN_SUB;
     if (const char* e = getenv("FIT_TL_SLICES")) slices = std::max(1, std::min(atoi(e), 512 / (TL_KS * shards)));
     if (const char* e = getenv("FIT_TL_MINSUB")) tl_min_sub = std::max(1, atoi(e));
     if (runs < 1)
         return fail(FIT_E_INVAL, "partition component of %d nodes is too large for the timeline "
                                  "commit's LDS", maxlen);
-    float ms;
-    for (;;) {
-        int64_t blocks = 0, slots = 0, cand_n = 0, evals = 0;
-        int epl = 1;
-        bool any = false;
-        for (int k = 0; k < C; ++k) {
-            CompPlan& P = c->h_plan.p[k];
-            P.k0 = 0;
-            memset(&P, 0, sizeof P);
-            P.nb = c->nb[k];
-            P.ne = c->nb[k + 1];
-            const int32_t len = P.ne - P.nb;
-            const int32_t per = (len + shards - 1) / shards;
-            P.sb = std::min(P.ne, P.nb + per * srank);
-            P.se = std::min(P.ne, P.sb + per);
-            // more, shorter block-slices than the plain fit: a run walk costs more per node, so
-            // the scan wants more waves in flight; candidate entries per job stay <= 256
-            P.ks = TL_KS;
-            P.sub = std::max(tl_min_sub, (per + SCAN_WAVES * slices - 1) / (SCAN_WAVES * slices));
-            P.nslice = std::max(1, (per + SCAN_WAVES * P.sub - 1) / (SCAN_WAVES * P.sub));
-            epl = std::max(epl, (shards * P.nslice * TL_KS + 63) / 64);
-            P.jbase = cur[k];
-            P.w = std::min(win[k], jb[k + 1] - cur[k]);
-            P.blk0 = (int32_t)blocks;
-            P.cand_off = cand_n;
-            P.slot0 = (int32_t)slots;
-            if (P.w > 0) {
-                any = true;
-                blocks += (int64_t)((P.w + SCAN_JOBS - 1) / SCAN_JOBS) * P.nslice;
-                cand_n += (int64_t)P.w * P.nslice * TL_KS;
-                slots += P.w;
-                evals += (int64_t)P.w * (P.se - P.sb);
-            }
-        }
-        if (!any) break;
-        S.rounds++;
-        S.evals += evals;
-        if (c->cand.ensure((size_t)cand_n * shards) || c->bnd.ensure(slots) ||
-            c->wjob.ensure(slots))
-            return FIT_E_OOM;
-        HIP_TRY(hipMemcpyAsync(c->plan.p, c->h_plan.p, sizeof(CompPlan) * C, hipMemcpyHostToDevice,
-                               st));
-        HIP_TRY(hipMemsetAsync(c->bnd.p, 0xff, sizeof(uint64_t) * slots, st));
-        HIP_TRY(hipEventRecord(c->ev[0], st));
-        HIP_TRY(launch_scan_tl((int)blocks, st, c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem,
-                               gpu, wall, part, c->plan.p, C, c->cand.p + (size_t)srank * cand_n,
-                               c->bnd.p, c->wjob.p, c->tl_slots, c->tl_slot_min));
-        HIP_TRY(hipEventRecord(c->ev[1], st));
-        if (node_sharded) {
-            rc = xchg(c, FIT_XCHG_ALLGATHER_U64, c->cand.p, cand_n);
-            if (!rc) rc = xchg(c, FIT_XCHG_MIN_U64, c->bnd.p, slots);
-            if (rc) return rc;
-        }
-        HIP_TRY(hipEventRecord(c->ev[2], st));
-        HIP_TRY(launch_commit_tl(C, epl, lds, st, c->slab.p, c->tlhdr.p, c->plan.p, c->cand.p,
-                                 cand_n, shards, c->bnd.p, c->wjob.p, c->perm.p, out, outs,
-                                 c->res.p, c->tl_slots, runs));
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-        HIP_TRY(hipMemcpyAsync(c->h_res.p, c->res.p, sizeof(CommitResult) * C,
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        S.ms_scan += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
-        S.ms_exchange += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        S.ms_commit += ms;
-        for (int k = 0; k < C; ++k) {
-            const CompPlan& P = c->h_plan.p[k];
-            if (P.w == 0) continue;
-            const CommitResult& R = c->h_res.p[k];
-            if (R.done < 0 || R.done > P.w)
-                return fail(FIT_E_HIP, "commit returned %d of window %d", R.done, P.w);
-            cur[k] += R.done;
-            S.placed += R.placed;
-            if (R.stop == 1) S.stops_rescan++;
-            if (R.stop == 2) S.stops_dirty++;
-            const int32_t nw = R.stop ? 2 * R.done : 2 * P.w;
-            win[k] = std::max(c->wmin, std::min(c->wmax, nw));
-        }
-    }
-    S.ms_device = S.ms_scan + S.ms_exchange + S.ms_commit;
+    rc = run_rounds(
+        c, jb, std::vector<char>(C, 1), node_sharded, TL_KS, slices, tl_min_sub,
+        [&](int blocks, uint64_t* cand) {
+            return launch_scan_tl(blocks, st, c->slab.p, c->tlhdr.p, c->jl.p, cpu, mem, gpu, wall, part,
+                                  c->plan.p, C, cand, c->bnd.p, c->wjob.p, c->tl_slots, c->tl_slot_min);
+        },
+        [&](int epl, int32_t, int64_t cand_n, int nshards) {
+            return launch_commit_tl(C, epl, lds, st, c->slab.p, c->tlhdr.p, c->plan.p, c->cand.p, cand_n,
+                                    nshards, c->bnd.p, c->wjob.p, c->perm.p, out, outs, c->res.p, c->tl_slots,
+                                    runs);
+        },
+        S);
+    if (rc) return rc;
     S.unplaced = J - S.placed - S.rejected;
     S.ms_total = now_ms() - t0;
     if (stats) *stats = S;
@@ -1499,13 +1290,22 @@ static_assert(sizeof(fit_why) == 32, "fit_why is 32 bytes");
 // component passes a mixed wave adds
 constexpr int32_t kExplainSortJobs = 256;
 
-int explain_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
-                 const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out, int32_t* bad) {
+// A batch's job columns on the device (nk: nullptr without a nodes_k column).
+struct JobCols {
+    const int32_t *cpu, *mem, *gpu, *wall;
+    const uint16_t *part, *nk;
+};
+
+// The sequence fit_explain and fit_when share: the flag reset, classify() (rows' limit codes,
+// component per job, *bad), above kExplainSortJobs jobs of several components the jobs in
+// component order, then walk(components, job list, live count, job component ids).
+template <class Classify, class Walk>
+int query_impl(fit_ctx* c, int32_t J, int32_t* bad, Classify classify, Walk walk) {
     const int C = c->ncomp;
     hipStream_t st = c->st;
     if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
     HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    HIP_TRY(launch_explain_classify(st, c->d_ptab.p, c->np, cpu, mem, gpu, wall, part, nk, J, out, c->jcomp.p, bad));
+    HIP_TRY(classify());
     const int32_t *jl = nullptr, *live = nullptr;
     if (J > kExplainSortJobs && C > 1) {
         if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
@@ -1520,20 +1320,21 @@ int explain_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, 
     ExplainComps ec;
     ec.ncomp = C;
     for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
-    HIP_TRY(launch_explain(st, c->rec.p, ec, cpu, mem, gpu, wall, part, J, c->jcomp.p, jl, live,
-                           explain_slices(J, c->cls_maxn, c->cus), out));
+    HIP_TRY(walk(ec, jl, live));
     return 0;
 }
 
-int check_explain_args(fit_ctx* c, int32_t j, const void* a, const void* b, const void* d, const void* e,
-                       const void* f, const void* out) {
-    if (!c) return fail(FIT_E_INVAL, "null ctx");
-    if (j < 0) return fail(FIT_E_INVAL, "j=%d", j);
-    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
-    if (c->collective()) return fail(FIT_E_STATE, "fit_explain on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
-    if (c->have_tl) return fail(FIT_E_STATE, "fit_explain while a timeline is loaded");
-    if (j > 0 && (!a || !b || !d || !e || !f || !out)) return fail(FIT_E_INVAL, "bad job arrays");
-    return 0;
+int explain_impl(fit_ctx* c, int32_t J, const JobCols& d, fit_why* out, int32_t* bad) {
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_explain_classify(c->st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, J,
+                                           out, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_explain(c->st, c->rec.p, ec, d.cpu, d.mem, d.gpu, d.wall, d.part, J, c->jcomp.p, jl, live,
+                                  explain_slices(J, c->cls_maxn, c->cus), out);
+        });
 }
 
 // --------------------------------------------------------------------------- fit_when
@@ -1555,43 +1356,118 @@ static_assert(sizeof(fit_eta) == 32, "fit_eta is 32 bytes");
 // is latency-bound and wants the waves — 1,024 jobs on C5: 0.307 ms at 32, DESIGN.md §3.12 at 4
 constexpr int kWhenMinNodes = 4;
 
-int when_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
-              const int32_t* wall, const uint16_t* part, fit_eta* out, int32_t* bad) {
-    const int C = c->ncomp;
-    hipStream_t st = c->st;
-    if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
-    HIP_TRY(launch_when_classify(st, c->d_ptab.p, c->np, cpu, mem, gpu, wall, part, J, c->tl_slot_min, out,
-                                 c->jcomp.p, bad));
-    const int32_t *jl = nullptr, *live = nullptr;
-    if (J > kExplainSortJobs && C > 1) {
-        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
-            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
-            return FIT_E_OOM;
-        int32_t* g = c->jls.p + joblists_scratch_ints(J);
-        int32_t* jbd = g + 2;
-        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
-        jl = c->jl.p;
-        live = jbd + C;  // jobs that have a component
-    }
-    ExplainComps ec;
-    ec.ncomp = C;
-    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
-    HIP_TRY(launch_when(st, c->tlhdr.p, c->slab.p, ec, c->tl_slots, c->tl_slot_min, cpu, mem, gpu, part, J,
-                        c->jcomp.p, jl, live, explain_slices(J, c->cls_maxn, c->cus, kWhenMinNodes), out));
+int when_impl(fit_ctx* c, int32_t J, const JobCols& d, fit_eta* out, int32_t* bad) {
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_when_classify(c->st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, J,
+                                        c->tl_slot_min, out, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_when(c->st, c->tlhdr.p, c->slab.p, ec, c->tl_slots, c->tl_slot_min, d.cpu, d.mem, d.gpu,
+                               d.part, J, c->jcomp.p, jl, live,
+                               explain_slices(J, c->cls_maxn, c->cus, kWhenMinNodes), out);
+        });
+}
+
+// The tests every entry point that takes a job batch makes, in the order its callers see them.
+// query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
+// sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
+int check_job_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, const char* query, int tl) {
+    if (!c) return fail(FIT_E_INVAL, "null ctx");
+    if (query && j < 0) return fail(FIT_E_INVAL, "j=%d", j);
+    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
+    if (query && c->collective())
+        return fail(FIT_E_STATE, "%s on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)", query);
+    if (tl < 0 && c->have_tl) return fail(FIT_E_STATE, "%s while a timeline is loaded", query);
+    if (tl > 0 && !c->have_tl) return fail(FIT_E_STATE, "fit_load_timeline not called");
+    if (j < 0 || (j > 0 && std::find(arrays.begin(), arrays.end(), nullptr) != arrays.end()))
+        return fail(FIT_E_INVAL, "bad job arrays");
     return 0;
 }
 
-int check_when_args(fit_ctx* c, int32_t j, const void* a, const void* b, const void* d, const void* e,
-                    const void* f, const void* out) {
-    if (!c) return fail(FIT_E_INVAL, "null ctx");
-    if (j < 0) return fail(FIT_E_INVAL, "j=%d", j);
-    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
-    if (c->collective()) return fail(FIT_E_STATE, "fit_when on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
-    if (!c->have_tl) return fail(FIT_E_STATE, "fit_load_timeline not called");
-    if (j > 0 && (!a || !b || !d || !e || !f || !out)) return fail(FIT_E_INVAL, "bad job arrays");
+// fit_place, fit_explain, fit_when: the batch's columns packed in pinned memory and sent in ONE
+// copy (the previous call's copy is complete: each of them ends with a synchronisation).  Four
+// int32 columns, then part and, if given, nodes_k, each rounded up to 4 bytes.
+int stage_packed(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                 const int32_t* wall, const uint16_t* part, const uint16_t* nk, JobCols& d) {
+    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j, bh4 = (bh + 3) & ~(size_t)3;
+    const size_t tot = 4 * b + 2 * bh4;
+    if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot)) return FIT_E_OOM;
+    uint8_t* h = c->h_jpack.p;
+    memcpy(h, cpu, b);
+    memcpy(h + b, mem, b);
+    memcpy(h + 2 * b, gpu, b);
+    memcpy(h + 3 * b, wall, b);
+    memcpy(h + 4 * b, part, bh);
+    if (nk) memcpy(h + 4 * b + bh4, nk, bh);
+    HIP_TRY(hipMemcpyAsync(c->jpack.p, h, nk ? tot : 4 * b + bh4, hipMemcpyHostToDevice, c->st));
+    const uint8_t* p = c->jpack.p;
+    d = {(const int32_t*)p, (const int32_t*)(p + b), (const int32_t*)(p + 2 * b), (const int32_t*)(p + 3 * b),
+         (const uint16_t*)(p + 4 * b), nk ? (const uint16_t*)(p + 4 * b + bh4) : nullptr};
     return 0;
 }
+
+// fit_place above kPackJobs and fit_place_tl: one copy per column into the context's job columns
+// (has_nk: the entry point has a nodes_k column at all).
+int stage_columns(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                  const int32_t* wall, const uint16_t* part, bool has_nk, const uint16_t* nk, JobCols& d) {
+    const size_t m = std::max(j, 1), b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j;
+    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) ||
+        c->jpart.ensure(m) || (has_nk && c->jk.ensure(m)))
+        return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jpart.p, part, bh, hipMemcpyHostToDevice, c->st));
+    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, bh, hipMemcpyHostToDevice, c->st));
+    d = {c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, c->jpart.p, nk ? c->jk.p : nullptr};
+    return 0;
+}
+
+// fit_explain / fit_when from host memory: the columns in one copy, impl(columns, rows, flag) with
+// the flag word behind the rows so that rows and flag come back in ONE copy, a spinning wait for a
+// batch of k_small's size, the flag test (bad(): the entry point's error) and the rows out.
+template <class Row, class Impl, class Bad>
+int query_host(fit_ctx* c, QueryBufs<Row>& Q, int32_t j, const int32_t* cpu, const int32_t* mem,
+               const int32_t* gpu, const int32_t* wall, const uint16_t* part, const uint16_t* nk, Row* out,
+               Impl impl, Bad bad) {
+    HIP_TRY(hipSetDevice(c->device));
+    JobCols d;
+    int rc = stage_packed(c, j, cpu, mem, gpu, wall, part, nk, d);
+    if (rc) return rc;
+    if (Q.out.ensure((size_t)j + 1) || Q.h.ensure((size_t)j + 1)) return FIT_E_OOM;
+    rc = impl(c, j, d, Q.out.p, reinterpret_cast<int32_t*>(Q.out.p + j));
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(Q.h.p, Q.out.p, sizeof(Row) * ((size_t)j + 1), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(j <= SMALL_ARGJ ? sync_small(c) : hipStreamSynchronize(c->st));
+    if (Q.h.p[j].code) return bad();
+    memcpy(out, Q.h.p, sizeof(Row) * j);
+    return 0;
+}
+
+// The same on device columns and rows: only the flag word comes back, and an event pair around the
+// launches gives the device time (Q.ms).
+template <class Row, class Impl, class Bad>
+int query_device(fit_ctx* c, QueryBufs<Row>& Q, int32_t j, const JobCols& d, Row* out, Impl impl, Bad bad) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (Q.bad.ensure(1) || Q.h.ensure(1)) return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], c->st));
+    const int rc = impl(c, j, d, out, Q.bad.p);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev[1], c->st));
+    HIP_TRY(hipMemcpyAsync(Q.h.p, Q.bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (Q.h.p[0].code) return bad();
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    Q.ms = ms;
+    return 0;
+}
+
+int bad_explain_job() { return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K); }
+int bad_when_job() { return fail(FIT_E_INVAL, "a job has a negative demand"); }
 
 int load_timeline_impl(fit_ctx* c, int32_t slots, int32_t slot_min, int64_t ne) {
     if (c->tlhdr.ensure(std::max(c->nn, 1)) ||
@@ -1774,8 +1650,9 @@ void fit_destroy(fit_ctx* ctx) {
     delete ctx;
 }
 
-int fit_load_nodes(fit_ctx* c, int32_t n, const int32_t* cpu, const int32_t* mem,
-                   const int32_t* gpu, const int32_t* av, const uint32_t* mask) {
+// fit_load_nodes / fit_load_nodes_device: the argument test and the five columns into col_*.
+static int load_node_cols(fit_ctx* c, int32_t n, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* av, const uint32_t* mask, hipMemcpyKind kind) {
     if (!c) return fail(FIT_E_INVAL, "null ctx");
     if (n < 0 || n > FIT_MAX_NODES || (n > 0 && (!cpu || !mem || !gpu || !av || !mask)))
         return fail(FIT_E_INVAL, "bad node arrays");
@@ -1785,31 +1662,28 @@ int fit_load_nodes(fit_ctx* c, int32_t n, const int32_t* cpu, const int32_t* mem
     HIP_TRY(hipSetDevice(c->device));
     if (alloc_cols(c, n)) return FIT_E_OOM;
     const size_t b = sizeof(int32_t) * n;
-    HIP_TRY(hipMemcpyAsync(c->col_cpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_mem.p, mem, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_gpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_av.p, av, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_mask.p, mask, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->col_cpu.p, cpu, b, kind, c->st));
+    HIP_TRY(hipMemcpyAsync(c->col_mem.p, mem, b, kind, c->st));
+    HIP_TRY(hipMemcpyAsync(c->col_gpu.p, gpu, b, kind, c->st));
+    HIP_TRY(hipMemcpyAsync(c->col_av.p, av, b, kind, c->st));
+    HIP_TRY(hipMemcpyAsync(c->col_mask.p, mask, b, kind, c->st));
+    return 0;
+}
+
+int fit_load_nodes(fit_ctx* c, int32_t n, const int32_t* cpu, const int32_t* mem,
+                   const int32_t* gpu, const int32_t* av, const uint32_t* mask) {
+    const int rc = load_node_cols(c, n, cpu, mem, gpu, av, mask, hipMemcpyHostToDevice);
+    if (rc) return rc;
     c->h_mask.assign(mask, mask + n);
     return load_nodes_common(c, n);
 }
 
 int fit_load_nodes_device(fit_ctx* c, int32_t n, const int32_t* cpu, const int32_t* mem,
                           const int32_t* gpu, const int32_t* av, const uint32_t* mask) {
-    if (!c) return fail(FIT_E_INVAL, "null ctx");
-    if (n < 0 || n > FIT_MAX_NODES || (n > 0 && (!cpu || !mem || !gpu || !av || !mask)))
-        return fail(FIT_E_INVAL, "bad node arrays");
-    c->have_nodes = c->have_tl = false;  // see fit_load_nodes
-    HIP_TRY(hipSetDevice(c->device));
-    if (alloc_cols(c, n)) return FIT_E_OOM;
-    const size_t b = sizeof(int32_t) * n;
-    HIP_TRY(hipMemcpyAsync(c->col_cpu.p, cpu, b, hipMemcpyDeviceToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_mem.p, mem, b, hipMemcpyDeviceToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_gpu.p, gpu, b, hipMemcpyDeviceToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_av.p, av, b, hipMemcpyDeviceToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->col_mask.p, mask, b, hipMemcpyDeviceToDevice, c->st));
+    const int rc = load_node_cols(c, n, cpu, mem, gpu, av, mask, hipMemcpyDeviceToDevice);
+    if (rc) return rc;
     c->h_mask.resize(n);
-    HIP_TRY(hipMemcpyAsync(c->h_mask.data(), mask, b, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(c->h_mask.data(), mask, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
     return load_nodes_common(c, n);
 }
@@ -1832,12 +1706,9 @@ int fit_load_partitions(fit_ctx* c, int32_t p, const int32_t* max_time,
     return 0;
 }
 
-static int check_place_args(fit_ctx* c, int32_t j, const void* a, const void* b, const void* d,
-                            const void* e, const void* f, int32_t kmax, const void* out) {
-    if (!c) return fail(FIT_E_INVAL, "null ctx");
-    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
-    if (j < 0 || (j > 0 && (!a || !b || !d || !e || !f || !out)))
-        return fail(FIT_E_INVAL, "bad job arrays");
+static int check_place_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, nullptr, 0);
+    if (rc) return rc;
     if (kmax < 1 || kmax > FIT_MAX_K)
         return fail(FIT_E_INVAL, "kmax=%d outside [1, %d]", kmax, FIT_MAX_K);
     return 0;
@@ -1849,7 +1720,7 @@ constexpr int32_t kPackJobs = 16384;
 int fit_place(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
               const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
               int32_t* out, fit_stats* stats) {
-    int rc = check_place_args(c, j, cpu, mem, gpu, wall, part, kmax, out);
+    int rc = check_place_args(c, j, {cpu, mem, gpu, wall, part, out}, kmax);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // demands >= 0 and nodes_k <= kmax are checked on the device (k_prefilter): FIT_E_INVAL
@@ -1872,49 +1743,13 @@ int fit_place(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, con
         if (!done) return fail(FIT_E_HIP, "direct placement did not return its placements");
         return 0;
     }
-    const int32_t *dcpu, *dmem, *dgpu, *dwall;
-    const uint16_t *dpart, *dk = nullptr;
-    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j;
-    if (j <= kPackJobs) {
-        // a small batch (admission): the columns packed in pinned memory, ONE copy to the device
-        // (the previous call's copy is complete: every fit_place ends with a synchronisation)
-        const size_t bh4 = (bh + 3) & ~(size_t)3;
-        const size_t tot = 4 * b + 2 * bh4;
-        if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot)) return FIT_E_OOM;
-        uint8_t* h = c->h_jpack.p;
-        memcpy(h, cpu, b);
-        memcpy(h + b, mem, b);
-        memcpy(h + 2 * b, gpu, b);
-        memcpy(h + 3 * b, wall, b);
-        memcpy(h + 4 * b, part, bh);
-        if (nk) memcpy(h + 4 * b + bh4, nk, bh);
-        HIP_TRY(hipMemcpyAsync(c->jpack.p, h, nk ? tot : 4 * b + bh4, hipMemcpyHostToDevice, c->st));
-        uint8_t* d = c->jpack.p;
-        dcpu = (const int32_t*)d;
-        dmem = (const int32_t*)(d + b);
-        dgpu = (const int32_t*)(d + 2 * b);
-        dwall = (const int32_t*)(d + 3 * b);
-        dpart = (const uint16_t*)(d + 4 * b);
-        if (nk) dk = (const uint16_t*)(d + 4 * b + bh4);
-    } else {
-        if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) ||
-            c->jpart.ensure(m) || c->jk.ensure(m))
-            return FIT_E_OOM;
-        HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->jpart.p, part, bh, hipMemcpyHostToDevice, c->st));
-        if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, bh, hipMemcpyHostToDevice, c->st));
-        dcpu = c->jcpu.p;
-        dmem = c->jmem.p;
-        dgpu = c->jgpu.p;
-        dwall = c->jwall.p;
-        dpart = c->jpart.p;
-        if (nk) dk = c->jk.p;
-    }
+    // up to kPackJobs jobs (admission): the columns in ONE copy; above, one copy per column
+    JobCols d;
+    rc = j <= kPackJobs ? stage_packed(c, j, cpu, mem, gpu, wall, part, nk, d)
+                        : stage_columns(c, j, cpu, mem, gpu, wall, part, true, nk, d);
+    if (rc) return rc;
     bool done = false;
-    rc = place_impl(c, j, dcpu, dmem, dgpu, dwall, dpart, dk, kmax, c->out.p, stats, out, &done);
+    rc = place_impl(c, j, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, c->out.p, stats, out, &done);
     if (rc) return rc;
     if (done) return 0;  // the direct small placement copied the placements back with its stats
     HIP_TRY(hipMemcpyAsync(out, c->out.p, sizeof(int32_t) * j * kmax, hipMemcpyDeviceToHost,
@@ -1926,7 +1761,7 @@ int fit_place(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, con
 int fit_place_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem,
                      const int32_t* gpu, const int32_t* wall, const uint16_t* part,
                      const uint16_t* nk, int32_t kmax, int32_t* out, fit_stats* stats) {
-    int rc = check_place_args(c, j, cpu, mem, gpu, wall, part, kmax, out);
+    int rc = check_place_args(c, j, {cpu, mem, gpu, wall, part, out}, kmax);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     rc = place_impl(c, j, cpu, mem, gpu, wall, part, nk, kmax, out, stats);
@@ -1937,119 +1772,43 @@ int fit_place_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* m
 
 int fit_explain(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                 const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out) {
-    int rc = check_explain_args(c, j, cpu, mem, gpu, wall, part, out);
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_explain", -1);
     if (rc || j == 0) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // the columns packed in pinned memory, ONE copy to the device (as fit_place's small batches)
-    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j, bh4 = (bh + 3) & ~(size_t)3;
-    const size_t tot = 4 * b + 2 * bh4;
-    if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot) || c->ex_out.ensure((size_t)j + 1) ||
-        c->h_ex.ensure((size_t)j + 1))
-        return FIT_E_OOM;
-    uint8_t* h = c->h_jpack.p;
-    memcpy(h, cpu, b);
-    memcpy(h + b, mem, b);
-    memcpy(h + 2 * b, gpu, b);
-    memcpy(h + 3 * b, wall, b);
-    memcpy(h + 4 * b, part, bh);
-    if (nk) memcpy(h + 4 * b + bh4, nk, bh);
-    HIP_TRY(hipMemcpyAsync(c->jpack.p, h, nk ? tot : 4 * b + bh4, hipMemcpyHostToDevice, c->st));
-    const uint8_t* d = c->jpack.p;
-    // the flag word behind the rows: rows and flag come back in ONE copy
-    int32_t* bad = reinterpret_cast<int32_t*>(c->ex_out.p + j);
-    rc = explain_impl(c, j, (const int32_t*)d, (const int32_t*)(d + b), (const int32_t*)(d + 2 * b),
-                      (const int32_t*)(d + 3 * b), (const uint16_t*)(d + 4 * b),
-                      nk ? (const uint16_t*)(d + 4 * b + bh4) : nullptr, c->ex_out.p, bad);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_ex.p, c->ex_out.p, sizeof(fit_why) * ((size_t)j + 1), hipMemcpyDeviceToHost,
-                           c->st));
-    HIP_TRY(j <= SMALL_ARGJ ? sync_small(c) : hipStreamSynchronize(c->st));
-    if (c->h_ex.p[j].code) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K);
-    memcpy(out, c->h_ex.p, sizeof(fit_why) * j);
-    return 0;
+    return query_host(c, c->ex, j, cpu, mem, gpu, wall, part, nk, out, explain_impl, bad_explain_job);
 }
 
 int fit_explain_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                        const int32_t* wall, const uint16_t* part, const uint16_t* nk, fit_why* out) {
-    int rc = check_explain_args(c, j, cpu, mem, gpu, wall, part, out);
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_explain", -1);
     if (rc || j == 0) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->ex_bad.ensure(1) || c->h_ex.ensure(1)) return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[0], c->st));
-    rc = explain_impl(c, j, cpu, mem, gpu, wall, part, nk, out, c->ex_bad.p);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev[1], c->st));
-    HIP_TRY(hipMemcpyAsync(c->h_ex.p, c->ex_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    if (c->h_ex.p[0].code) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->ex_ms = ms;
-    return 0;
+    return query_device(c, c->ex, j, {cpu, mem, gpu, wall, part, nk}, out, explain_impl, bad_explain_job);
 }
 
 int fit_explain_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
-    if (c->ex_ms < 0) return fail(FIT_E_STATE, "no fit_explain_device yet");
-    *ms = c->ex_ms;
+    if (c->ex.ms < 0) return fail(FIT_E_STATE, "no fit_explain_device yet");
+    *ms = c->ex.ms;
     return 0;
 }
 
 int fit_when(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
              const int32_t* wall, const uint16_t* part, fit_eta* out) {
-    int rc = check_when_args(c, j, cpu, mem, gpu, wall, part, out);
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_when", 1);
     if (rc || j == 0) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // the columns packed in pinned memory, ONE copy to the device (as fit_explain)
-    const size_t b = sizeof(int32_t) * j, bh = sizeof(uint16_t) * j;
-    const size_t tot = 4 * b + bh;
-    if (c->jpack.ensure(tot) || c->h_jpack.ensure(tot) || c->wh_out.ensure((size_t)j + 1) ||
-        c->h_wh.ensure((size_t)j + 1))
-        return FIT_E_OOM;
-    uint8_t* h = c->h_jpack.p;
-    memcpy(h, cpu, b);
-    memcpy(h + b, mem, b);
-    memcpy(h + 2 * b, gpu, b);
-    memcpy(h + 3 * b, wall, b);
-    memcpy(h + 4 * b, part, bh);
-    HIP_TRY(hipMemcpyAsync(c->jpack.p, h, tot, hipMemcpyHostToDevice, c->st));
-    const uint8_t* d = c->jpack.p;
-    // the flag word behind the rows: rows and flag come back in ONE copy
-    int32_t* bad = reinterpret_cast<int32_t*>(c->wh_out.p + j);
-    rc = when_impl(c, j, (const int32_t*)d, (const int32_t*)(d + b), (const int32_t*)(d + 2 * b),
-                   (const int32_t*)(d + 3 * b), (const uint16_t*)(d + 4 * b), c->wh_out.p, bad);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_wh.p, c->wh_out.p, sizeof(fit_eta) * ((size_t)j + 1), hipMemcpyDeviceToHost,
-                           c->st));
-    HIP_TRY(j <= SMALL_ARGJ ? sync_small(c) : hipStreamSynchronize(c->st));
-    if (c->h_wh.p[j].code) return fail(FIT_E_INVAL, "a job has a negative demand");
-    memcpy(out, c->h_wh.p, sizeof(fit_eta) * j);
-    return 0;
+    return query_host(c, c->wh, j, cpu, mem, gpu, wall, part, nullptr, out, when_impl, bad_when_job);
 }
 
 int fit_when_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                     const int32_t* wall, const uint16_t* part, fit_eta* out) {
-    int rc = check_when_args(c, j, cpu, mem, gpu, wall, part, out);
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_when", 1);
     if (rc || j == 0) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->wh_bad.ensure(1) || c->h_wh.ensure(1)) return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[0], c->st));
-    rc = when_impl(c, j, cpu, mem, gpu, wall, part, out, c->wh_bad.p);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev[1], c->st));
-    HIP_TRY(hipMemcpyAsync(c->h_wh.p, c->wh_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    if (c->h_wh.p[0].code) return fail(FIT_E_INVAL, "a job has a negative demand");
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->wh_ms = ms;
-    return 0;
+    return query_device(c, c->wh, j, {cpu, mem, gpu, wall, part, nullptr}, out, when_impl, bad_when_job);
 }
 
 int fit_when_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
-    if (c->wh_ms < 0) return fail(FIT_E_STATE, "no fit_when_device yet");
-    *ms = c->wh_ms;
+    if (c->wh.ms < 0) return fail(FIT_E_STATE, "no fit_when_device yet");
+    *ms = c->wh.ms;
     return 0;
 }
 
@@ -2093,6 +1852,28 @@ int fit_partition_free(fit_ctx* c, int32_t p, int64_t* cpu, int64_t* mem, int64_
     return 0;
 }
 
+// fit_load_timeline / fit_load_timeline_device: the release events (ne of them; rel_off null: none)
+// into rel_*, then the run lists.
+static int load_releases(fit_ctx* c, int32_t slots, int32_t slot_min, const int32_t* rel_off, int64_t ne,
+                         const int32_t* rel_slot, const int32_t* rel_cpu, const int32_t* rel_mem,
+                         const int32_t* rel_gpu, hipMemcpyKind kind) {
+    const size_t m = std::max<int64_t>(ne, 1);
+    if (c->rel_off.ensure(c->n + 1) || c->rel_slot.ensure(m) || c->rel_cpu.ensure(m) || c->rel_mem.ensure(m) ||
+        c->rel_gpu.ensure(m))
+        return FIT_E_OOM;
+    if (rel_off) {
+        HIP_TRY(hipMemcpyAsync(c->rel_off.p, rel_off, sizeof(int32_t) * (c->n + 1), kind, c->st));
+        if (ne > 0) {
+            const size_t b = sizeof(int32_t) * ne;
+            HIP_TRY(hipMemcpyAsync(c->rel_slot.p, rel_slot, b, kind, c->st));
+            HIP_TRY(hipMemcpyAsync(c->rel_cpu.p, rel_cpu, b, kind, c->st));
+            HIP_TRY(hipMemcpyAsync(c->rel_mem.p, rel_mem, b, kind, c->st));
+            HIP_TRY(hipMemcpyAsync(c->rel_gpu.p, rel_gpu, b, kind, c->st));
+        }
+    }
+    return load_timeline_impl(c, slots, slot_min, rel_off ? ne : -1);
+}
+
 int fit_load_timeline(fit_ctx* c, int32_t slots, int32_t slot_min, const int32_t* rel_off,
                       const int32_t* rel_slot, const int32_t* rel_cpu, const int32_t* rel_mem,
                       const int32_t* rel_gpu) {
@@ -2108,22 +1889,8 @@ int fit_load_timeline(fit_ctx* c, int32_t slots, int32_t slot_min, const int32_t
         if (ne > 0 && (!rel_slot || !rel_cpu || !rel_mem || !rel_gpu))
             return fail(FIT_E_INVAL, "null release arrays");
     }
-    if (c->rel_off.ensure(c->n + 1) || c->rel_slot.ensure(std::max<int64_t>(ne, 1)) ||
-        c->rel_cpu.ensure(std::max<int64_t>(ne, 1)) || c->rel_mem.ensure(std::max<int64_t>(ne, 1)) ||
-        c->rel_gpu.ensure(std::max<int64_t>(ne, 1)))
-        return FIT_E_OOM;
-    if (rel_off) {
-        HIP_TRY(hipMemcpyAsync(c->rel_off.p, rel_off, sizeof(int32_t) * (c->n + 1),
-                               hipMemcpyHostToDevice, c->st));
-        if (ne > 0) {
-            const size_t b = sizeof(int32_t) * ne;
-            HIP_TRY(hipMemcpyAsync(c->rel_slot.p, rel_slot, b, hipMemcpyHostToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_cpu.p, rel_cpu, b, hipMemcpyHostToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_mem.p, rel_mem, b, hipMemcpyHostToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_gpu.p, rel_gpu, b, hipMemcpyHostToDevice, c->st));
-        }
-    }
-    return load_timeline_impl(c, slots, slot_min, rel_off ? ne : -1);
+    return load_releases(c, slots, slot_min, rel_off, ne, rel_slot, rel_cpu, rel_mem, rel_gpu,
+                         hipMemcpyHostToDevice);
 }
 
 int fit_load_timeline_device(fit_ctx* c, int32_t slots, int32_t slot_min, const int32_t* rel_off,
@@ -2134,55 +1901,25 @@ int fit_load_timeline_device(fit_ctx* c, int32_t slots, int32_t slot_min, const 
     if (n_rel < 0 || (n_rel > 0 && (!rel_off || !rel_slot || !rel_cpu || !rel_mem || !rel_gpu)))
         return fail(FIT_E_INVAL, "bad release arrays");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->rel_off.ensure(c->n + 1) || c->rel_slot.ensure(std::max<int64_t>(n_rel, 1)) ||
-        c->rel_cpu.ensure(std::max<int64_t>(n_rel, 1)) ||
-        c->rel_mem.ensure(std::max<int64_t>(n_rel, 1)) || c->rel_gpu.ensure(std::max<int64_t>(n_rel, 1)))
-        return FIT_E_OOM;
-    if (rel_off) {
-        HIP_TRY(hipMemcpyAsync(c->rel_off.p, rel_off, sizeof(int32_t) * (c->n + 1),
-                               hipMemcpyDeviceToDevice, c->st));
-        if (n_rel > 0) {
-            const size_t b = sizeof(int32_t) * n_rel;
-            HIP_TRY(hipMemcpyAsync(c->rel_slot.p, rel_slot, b, hipMemcpyDeviceToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_cpu.p, rel_cpu, b, hipMemcpyDeviceToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_mem.p, rel_mem, b, hipMemcpyDeviceToDevice, c->st));
-            HIP_TRY(hipMemcpyAsync(c->rel_gpu.p, rel_gpu, b, hipMemcpyDeviceToDevice, c->st));
-        }
-    }
-    return load_timeline_impl(c, slots, slot_min, rel_off ? n_rel : -1);
-}
-
-static int check_place_tl_args(fit_ctx* c, int32_t j, const void* a, const void* b,
-                               const void* d, const void* e, const void* f, const void* out,
-                               const void* outs) {
-    if (!c) return fail(FIT_E_INVAL, "null ctx");
-    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
-    if (!c->have_tl) return fail(FIT_E_STATE, "fit_load_timeline not called");
-    if (j < 0 || (j > 0 && (!a || !b || !d || !e || !f || !out || !outs)))
-        return fail(FIT_E_INVAL, "bad job arrays");
-    return 0;
+    return load_releases(c, slots, slot_min, rel_off, n_rel, rel_slot, rel_cpu, rel_mem, rel_gpu,
+                         hipMemcpyDeviceToDevice);
 }
 
 int fit_place_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem,
                  const int32_t* gpu, const int32_t* wall, const uint16_t* part, int32_t* out_node,
                  int32_t* out_start, fit_stats* stats) {
-    int rc = check_place_tl_args(c, j, cpu, mem, gpu, wall, part, out_node, out_start);
+    int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, nullptr, 1);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // demands >= 0 are checked on the device (k_prefilter): FIT_E_INVAL
     size_t m = std::max(j, 1);
-    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) ||
-        c->jpart.ensure(m) || c->out.ensure(m) || c->outs.ensure(m))
-        return FIT_E_OOM;
-    const size_t b = sizeof(int32_t) * j;
-    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jpart.p, part, sizeof(uint16_t) * j, hipMemcpyHostToDevice, c->st));
-    rc = place_tl_impl(c, j, c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, c->jpart.p, c->out.p,
-                       c->outs.p, stats);
+    JobCols d;
+    rc = stage_columns(c, j, cpu, mem, gpu, wall, part, false, nullptr, d);
     if (rc) return rc;
+    if (c->out.ensure(m) || c->outs.ensure(m)) return FIT_E_OOM;
+    rc = place_tl_impl(c, j, d.cpu, d.mem, d.gpu, d.wall, d.part, c->out.p, c->outs.p, stats);
+    if (rc) return rc;
+    const size_t b = sizeof(int32_t) * j;
     HIP_TRY(hipMemcpyAsync(out_node, c->out.p, b, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipMemcpyAsync(out_start, c->outs.p, b, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
@@ -2192,7 +1929,7 @@ int fit_place_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem,
 int fit_place_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem,
                         const int32_t* gpu, const int32_t* wall, const uint16_t* part,
                         int32_t* out_node, int32_t* out_start, fit_stats* stats) {
-    int rc = check_place_tl_args(c, j, cpu, mem, gpu, wall, part, out_node, out_start);
+    int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, nullptr, 1);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     rc = place_tl_impl(c, j, cpu, mem, gpu, wall, part, out_node, out_start, stats);
@@ -2209,10 +1946,7 @@ int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {
     const size_t cells = (size_t)c->n * c->tl_slots;
     DBuf<int32_t> d[3];
     for (auto& x : d)
-        if (x.ensure(std::max<size_t>(cells, 1))) {
-            for (auto& y : d) y.release();
-            return FIT_E_OOM;
-        }
+        if (x.ensure(std::max<size_t>(cells, 1))) return FIT_E_OOM;
     // rows of nodes outside every partition (mask 0) are not on the device: -1, like unusable
     int rc = 0;
     for (auto& x : d)
@@ -2224,7 +1958,6 @@ int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {
         hipMemcpyAsync(gpu, d[2].p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
         hipStreamSynchronize(c->st) != hipSuccess)
         rc = fail(FIT_E_HIP, "timeline read-back failed");
-    for (auto& x : d) x.release();
     return rc;
 }
 

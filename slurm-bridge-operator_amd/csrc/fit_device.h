@@ -1,6 +1,7 @@
 // fit_device.h — data layouts shared by the HIP kernels and the host engine.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <hip/hip_vector_types.h>
 #include <stdint.h>
 
 namespace fitgpu {
@@ -222,5 +223,99 @@ struct TripRec {  // the launch's first trip (claim 0 -> 1); plain stores, read 
     unsigned long long waited;  // realtime ticks (10 ns) the wait lasted
     unsigned long long when;    // realtime at the trip, minus the launch's start stamp
 };
+
+
+// ---- launch functions and sizing queries of the .hip files, as the host engine calls them ------
+hipError_t launch_scan(int blocks, hipStream_t st, const NodeRec* rec, const int32_t* jl,
+                       const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                       const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
+                       const CompPlan* plan, int ncomp, uint64_t* cand, uint64_t* bnd,
+                       JobRec* wjob);
+hipError_t launch_commit(int ncomp, int epl, size_t lds_bytes, hipStream_t st, NodeRec* rec,
+                         const CompPlan* plan, const uint64_t* cand, int64_t rank_stride,
+                         int nranks, const uint64_t* bnd, const JobRec* wjob, int32_t* out,
+                         int kmax, CommitResult* res);
+hipError_t launch_prefilter(hipStream_t st, const int32_t* jcpu, const int32_t* jmem,
+                            const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
+                            int32_t nj, int32_t kmax, const int32_t* ptab, int32_t np,
+                            int32_t* out, int8_t* jcomp);
+size_t joblists_scratch_ints(int32_t nj);
+hipError_t launch_joblists(hipStream_t st, const int8_t* jcomp, int32_t nj, int ncomp,
+                           int32_t* scratch, int32_t* g, int32_t* jb, int32_t* mb, int32_t* jl,
+                           int32_t* jpk);
+hipError_t launch_small_args(hipStream_t st, int ncomp, NodeRec* rec, const SmallComps& C, const int32_t* ptab,
+                             int32_t np, const SmallBatch& B, bool has_nk, int32_t nj, int32_t kmax, int32_t* out,
+                             int32_t* stat);
+hipError_t launch_small(hipStream_t st, int ncomp, NodeRec* rec, const SmallComps& C,
+                        const int32_t* ptab, int32_t np, const int32_t* jcpu, const int32_t* jmem,
+                        const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                        const uint16_t* jk, int32_t nj, int32_t kmax, int32_t* out, int32_t* stat);
+hipError_t launch_gather_nodes(hipStream_t st, const int32_t* cpu, const int32_t* mem,
+                               const int32_t* gpu, const int32_t* av, const uint32_t* mask,
+                               const int32_t* perm, int32_t nn, NodeRec* rec);
+hipError_t launch_scatter_nodes(hipStream_t st, const NodeRec* rec, int32_t nn, int32_t* cpu,
+                                int32_t* mem, int32_t* gpu);
+size_t engine_lds_bytes(int32_t max_component_nodes);
+// demand-class engine (fit_class.hip)
+size_t class_lds_bytes(int32_t max_component_nodes);
+int class_max();
+int class_table_slots();
+size_t class_slot_bytes();
+int class_max_nodes();
+hipError_t launch_classify(hipStream_t st, const int8_t* jcomp, const int32_t* jcpu, const int32_t* jmem,
+                           const int32_t* jgpu, const uint16_t* jpart, int32_t nj, void* tab, int4* dem,
+                           int32_t* ncls, int16_t* jcls);
+hipError_t launch_class(hipStream_t st, int ncomp, size_t lds, NodeRec* rec, const int32_t* nbv, uint32_t owned,
+                        const int32_t* jb, const int32_t* jl, const int32_t* jwall, const uint16_t* jk,
+                        const int16_t* jcls, const int4* dem, const int32_t* ncls, int32_t kmax, int32_t* out,
+                        CompOut* co, unsigned* err);
+hipError_t launch_class_out(hipStream_t st, int32_t* out, int64_t n, const NodeRec* rec);
+size_t engine_ctl_bytes();
+size_t engine_ctl_error_offset();
+size_t engine_ctl_trip_offset();
+size_t engine_ring_bytes();
+size_t engine_ring_tasks();
+int engine_ring_groups();
+int engine_blocks_per_cu(size_t lds);
+hipError_t launch_engine(int blocks, size_t lds, hipStream_t st, void* ctl, void* ring,
+                         const void* cs, void* co, CompPlan* plans, int ncomp, NodeRec* rec,
+                         const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
+                         const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                         const uint16_t* jk, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
+                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd);
+// time-windowed backfill (fit_timeline.hip)
+hipError_t launch_build_tl(hipStream_t st, const int32_t* cpu, const int32_t* mem,
+                           const int32_t* gpu, const int32_t* av, const uint32_t* mask,
+                           const int32_t* perm, int32_t nn, int32_t H, int32_t slot_min,
+                           const int32_t* off, const int32_t* rs, const int32_t* rc,
+                           const int32_t* rm, const int32_t* rg, Seg* slab, TlHdr* hdr,
+                           uint32_t* err);
+hipError_t launch_scan_tl(int blocks, hipStream_t st, const Seg* slab, const TlHdr* hdr,
+                          const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
+                          const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                          const CompPlan* plan, int ncomp, uint64_t* cand, uint64_t* bnd,
+                          JobRec* wjob, int32_t H, int32_t slot_min);
+size_t commit_tl_lds_bytes(int32_t max_component_nodes);
+int commit_tl_runs(int32_t max_component_nodes);
+hipError_t launch_commit_tl(int ncomp, int epl, size_t lds, hipStream_t st, Seg* slab,
+                            TlHdr* hdr, const CompPlan* plan, const uint64_t* cand,
+                            int64_t rank_stride, int nranks, const uint64_t* bnd,
+                            const JobRec* wjob, const int32_t* perm, int32_t* out, int32_t* outs,
+                            CommitResult* res, int32_t H, int32_t R);
+int engine_tl_runs(int32_t max_component_nodes);
+size_t engine_tl_lds_bytes(int32_t max_component_nodes);
+int engine_tl_blocks_per_cu(size_t lds, int mode);
+size_t engine_tl_scan_lds_bytes();
+hipError_t launch_engine_tl(int blocks, size_t lds, hipStream_t st, void* ctl, void* ring,
+                            const void* cs, void* co, CompPlan* plans, int ncomp, Seg* slab,
+                            TlHdr* hdr, const int32_t* jl, const int32_t* jcpu,
+                            const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                            const uint16_t* jpart, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
+                            const int32_t* perm, int32_t* out, int32_t* outs, int32_t H,
+                            int32_t slot_min, int32_t R, int64_t* wbusy, int mode,
+                            unsigned* resident, unsigned wd);
+hipError_t launch_expand_tl(hipStream_t st, const int32_t* perm, const Seg* slab,
+                            const TlHdr* hdr, int32_t nn, int32_t H, int32_t* oc, int32_t* om,
+                            int32_t* og);
 
 }  // namespace fitgpu

@@ -1,13 +1,13 @@
 """fit_explain on the GPU against a numpy restatement of DESIGN.md §2c (ref_explain below): exact
 counts on shapes that cross every wave, tile and slice edge of k_explain_count, consistency with
 what fit_place decided, FITS means placeable, the admitter's view (reservations), state errors."""
-import ctypes as C
 import threading
 
 import numpy as np
 import pytest
 
 import fitgpu
+from _devarray import DevArray
 from fitgpu import (FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
                     FIT_WHY_PARTITION, FIT_WHY_RESOURCES, WHY_DTYPE, Admitter, Engine, FitError, _lib, synth)
 
@@ -44,46 +44,6 @@ def ref_explain(cpu, mem, gpu, avail, mask, parts, jobs):
     code[live[:, 0] & (out["members"] > 0) & (out["fit"] < out["need"])] = FIT_WHY_RESOURCES
     out["code"] = code
     return out
-
-
-class DevArray:
-    """A numpy array's copy in device memory, through the HIP runtime libfitgpu.so resolved at load
-    time: hipMalloc & co looked up through the library's own handle, which searches its dependencies.
-    Not through torch: its wheel carries a HIP runtime of its own, and when the engine's runtime
-    started first in the process, torch's finds no GPU."""
-    _hip = None
-
-    @classmethod
-    def hip(cls):
-        if cls._hip is None:
-            cls._hip = C.CDLL(_lib.LIB_PATH)
-            cls._hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-            cls._hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-            cls._hip.hipFree.argtypes = [C.c_void_p]
-        return cls._hip
-
-    def __init__(self, a):
-        self.shape, self.dtype, self.nbytes, self.n = a.shape, a.dtype, max(a.nbytes, 4), a.size
-        self.p = C.c_void_p()
-        assert self.hip().hipMalloc(C.byref(self.p), self.nbytes) == 0
-        a = np.ascontiguousarray(a)
-        assert self.hip().hipMemcpy(self.p, C.c_void_p(a.ctypes.data), a.nbytes, 1) == 0  # host to device
-
-    def data_ptr(self):
-        return self.p.value
-
-    def numel(self):
-        return self.n
-
-    def numpy(self):
-        out = np.empty(self.shape, self.dtype)
-        assert self.hip().hipMemcpy(C.c_void_p(out.ctypes.data), self.p, out.nbytes, 2) == 0  # device to host
-        return out
-
-    def __del__(self):
-        if self.p:
-            self.hip().hipFree(self.p)
-            self.p = None
 
 
 def explain_both(e, jobs):

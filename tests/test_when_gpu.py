@@ -9,6 +9,7 @@ import pytest
 
 import _tl_cases
 import fitgpu
+from _devarray import DevArray
 from fitgpu import (ETA_DTYPE, FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM,
                     FIT_ETA_LIMIT_TIME, FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, Engine, FitError, _lib, synth)
 from oracle import pyoracle as po
@@ -18,45 +19,6 @@ pytestmark = pytest.mark.gpu
 INF = synth.INT32_MAX
 JOB_FIELDS = ("cpu", "mem", "gpu", "wall", "part", "nodes_k")
 REJECT_CODES = (FIT_ETA_PARTITION, FIT_ETA_LIMIT_TIME, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM)
-
-
-class DevArray:
-    """A numpy array's copy in device memory, through the HIP runtime libfitgpu.so resolved at load
-    time (as tests/test_explain_gpu.py: not through torch, whose wheel carries a HIP runtime of its
-    own)."""
-    _hip = None
-
-    @classmethod
-    def hip(cls):
-        if cls._hip is None:
-            cls._hip = C.CDLL(_lib.LIB_PATH)
-            cls._hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-            cls._hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-            cls._hip.hipFree.argtypes = [C.c_void_p]
-        return cls._hip
-
-    def __init__(self, a):
-        self.shape, self.dtype, self.nbytes, self.n = a.shape, a.dtype, max(a.nbytes, 4), a.size
-        self.p = C.c_void_p()
-        assert self.hip().hipMalloc(C.byref(self.p), self.nbytes) == 0
-        a = np.ascontiguousarray(a)
-        assert self.hip().hipMemcpy(self.p, C.c_void_p(a.ctypes.data), a.nbytes, 1) == 0  # host to device
-
-    def data_ptr(self):
-        return self.p.value
-
-    def numel(self):
-        return self.n
-
-    def numpy(self):
-        out = np.empty(self.shape, self.dtype)
-        assert self.hip().hipMemcpy(C.c_void_p(out.ctypes.data), self.p, out.nbytes, 2) == 0  # device to host
-        return out
-
-    def __del__(self):
-        if self.p:
-            self.hip().hipFree(self.p)
-            self.p = None
 
 
 def ref_when(tl, mask, parts, jobs, slot_min):
