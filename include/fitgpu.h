@@ -336,6 +336,68 @@ int fit_when_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_when_message(const fit_eta* e, char* buf, int32_t buflen);
 
+/* ---- how many more copies of a job fit now ---------------------------------
+ * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a
+ * partition takes of one shape, the resource that runs out first: fit_room judges each of J jobs
+ * ALONE against the context's current node table, as fit_explain does, and changes nothing.  A job
+ * is its per-node demand; there is no nodes_k (for a k-node job the row counts node shares: the
+ * largest number of k-node jobs is not floor(copies / k), §2e).  On a feasible member node
+ * (fit_explain's four terms) `per` = min over the resources r in {gpu, cpu, mem} with demand_r > 0
+ * of floor(free_r / demand_r), FIT_ROOM_UNBOUNDED if all three demands are 0; on any other node
+ * per = 0.  The binding resource of a feasible node is the first r in the order gpu, cpu, mem with
+ * demand_r > 0 and floor(free_r / demand_r) == per.  One 40-byte row per job. */
+#define FIT_ROOM_SOME 0        /* copies > 0: a fit_place of m one-node copies of this job alone   */
+                               /* places min(m, copies) of them                                     */
+#define FIT_ROOM_PARTITION 1   /* = FIT_WHY_PARTITION    these four: FIT_WHY_*'s numbers, rule and */
+#define FIT_ROOM_LIMIT_TIME 2  /* = FIT_WHY_LIMIT_TIME   order; every other field is 0, with       */
+#define FIT_ROOM_LIMIT_CPUS 3  /* = FIT_WHY_LIMIT_CPUS   best_node = -1                            */
+#define FIT_ROOM_LIMIT_MEM 4   /* = FIT_WHY_LIMIT_MEM                                              */
+#define FIT_ROOM_NO_NODES 5    /* members == 0 (= FIT_WHY_NO_NODES)                                */
+#define FIT_ROOM_NONE 6        /* copies == 0                                                      */
+#define FIT_ROOM_UNBOUNDED 2147483647 /* per of a feasible node for an all-zero demand (INT32_MAX) */
+/* Precedence: 1, 2, 3, 4, 5, 6, 0 (first match wins).  The row and the call share a name, so the
+ * row is a struct tag: `struct fit_room` in C and in C++. */
+struct fit_room {
+    int32_t code;       /* FIT_ROOM_*                                                          */
+    int32_t members;    /* as fit_why.members                                                  */
+    int32_t nodes;      /* feasible members; equals fit_why.fit                                */
+    int32_t best;       /* max of per over the members, 0 if none                              */
+    int64_t copies;     /* sum of per over the members (64 bits: cannot overflow)              */
+    int32_t best_node;  /* node id of a node with per == best > 0, the lowest on a tie; -1 if  */
+                        /* none                                                                */
+    int32_t by_gpu;     /* feasible members whose binding resource is gpu                      */
+    int32_t by_cpu;     /*   ... cpu                                                           */
+    int32_t by_mem;     /*   ... memory; the three sum to nodes, or are 0 for an all-zero      */
+                        /* demand                                                              */
+};
+/* Host pointers.  j == 0 returns 0 whatever the pointers are.  FIT_E_INVAL: NULL ctx / arrays,
+ * j < 0, a negative demand (the whole call fails).  FIT_E_STATE: before fit_load_nodes; while a
+ * timeline is loaded; on a context created with world > 1 or FIT_FLAG_COLLECTIVES.  Three bounded
+ * launches, no persistent grid: neither the per-GPU persistent-launch lock nor the watchdog. */
+int fit_room(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+             const int32_t* wall, const uint16_t* part, struct fit_room* out);
+/* Same with device pointers (inputs resident in HBM, the rows written in HBM; out 8-byte aligned). */
+int fit_room_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                    const int32_t* wall, const uint16_t* part, struct fit_room* out);
+/* Diagnostic, for measurement only (tools/room_bench.py): device time of the last successful
+ * fit_room_device on this context, in milliseconds (HIP events on the context's own stream around
+ * its launches).  FIT_E_STATE when there has been none. */
+int fit_room_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text, NUL-terminated into buf.  Host only: no device, no context.
+ * Returns the length written (without the NUL), or FIT_E_INVAL: NULL arguments, an unknown code,
+ * or a buffer too small for the text and its NUL (256 bytes always suffice).  The exact texts,
+ * <x> a decimal field of the row:
+ *   FIT_ROOM_SOME       "room for <copies> more on <nodes>/<members> nodes (at most <best> on one
+ *                        node): limited by gpu on <by_gpu>, cpu on <by_cpu>, memory on <by_mem>"
+ *                       — on one line, terms joined by ", "; a term whose count is 0 is left out,
+ *                       and with no term left the ": limited by " goes too
+ *     with best == FIT_ROOM_UNBOUNDED instead
+ *                       "no resource demand: unlimited room on <nodes>/<members> nodes"
+ *   FIT_ROOM_NONE       "no room now on any of <members> nodes"
+ *   FIT_ROOM_NO_NODES / LIMIT_TIME / LIMIT_CPUS / LIMIT_MEM / PARTITION: fit_why_message's texts of
+ *                       the codes with the same numbers, verbatim */
+int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen);
+
 /* ---- ingest / demand helpers (host code, mirrors of the reference Go functions) -------- */
 /* ParseDuration (pkg/slurm-agent/parse.go:36-109): 0 ok, FIT_E_UNLIMITED, FIT_E_PARSE. */
 int fit_parse_duration(const char* s, int64_t* out_ns);
@@ -517,6 +579,10 @@ int fit_admitter_set_ttl(fit_admitter* a, int32_t loads);
  * coalescer, so it waits for at most the batch being placed.  priority and flags are ignored.
  * n == 0 returns 0.  Errors as fit_explain. */
 int fit_admitter_explain(fit_admitter* a, const fit_admit_req* reqs, int32_t n, fit_why* out);
+/* fit_room of n requests against the same table, brought up to date exactly as
+ * fit_admitter_explain does; priority, flags and nodes_k are ignored.  n == 0 returns 0.  Errors
+ * as fit_room. */
+int fit_admitter_room(fit_admitter* a, const fit_admit_req* reqs, int32_t n, struct fit_room* out);
 /* Open reservations / requests queued for the next batch (monitoring, tests). */
 int fit_admitter_reservations(fit_admitter* a);
 int fit_admitter_pending(fit_admitter* a);

@@ -526,6 +526,25 @@ int fit_admitter_explain(fit_admitter* a, const fit_admit_req* reqs, int32_t n, 
     return fit_explain(a->ctx, n, cpu, mem, gpu, wall, part, nk, out);
 }
 
+int fit_admitter_room(fit_admitter* a, const fit_admit_req* reqs, int32_t n, struct fit_room* out) {
+    if (!a || n < 0 || (n > 0 && (!reqs || !out))) return fail(FIT_E_INVAL, "fit_admitter_room: bad arguments");
+    if (n == 0) return FIT_OK;
+    std::vector<int32_t> col((size_t)n * 4);
+    std::vector<uint16_t> part((size_t)n);
+    int32_t *cpu = col.data(), *mem = cpu + n, *gpu = mem + n, *wall = gpu + n;
+    for (int32_t i = 0; i < n; ++i) {
+        const fit_admit_req& q = reqs[i];
+        cpu[i] = q.cpu, mem[i] = q.mem_mib, gpu[i] = q.gpu, wall[i] = q.wall_min;
+        part[i] = q.part;
+    }
+    // fit_admitter_explain's lock and table: what the next batch would see
+    std::lock_guard<std::mutex> g(a->ctx_m);
+    int rc = a->take_over();
+    if (rc == FIT_OK) rc = a->push_engine();
+    if (rc != FIT_OK) return rc;
+    return fit_room(a->ctx, n, cpu, mem, gpu, wall, part.data(), out);
+}
+
 int fit_admitter_confirm(fit_admitter* a, int64_t ticket) {
     if (!a) return FIT_E_INVAL;
     std::lock_guard<std::mutex> g(a->ctx_m);

@@ -316,6 +316,7 @@ struct fit_ctx : CtxHandles {
     // pinned copy and the *_ms diagnostic of each
     QueryBufs<fit_why> ex;
     QueryBufs<fit_eta> wh;
+    QueryBufs<struct fit_room> rm;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1370,6 +1371,38 @@ int when_impl(fit_ctx* c, int32_t J, const JobCols& d, fit_eta* out, int32_t* ba
         });
 }
 
+// --------------------------------------------------------------------------- fit_room
+// fit_explain's sequence with the room count in place of the shortage count
+// — classify, (a long queue: the jobs in component order), count, finalise.  Bounded launches on
+// the context's stream, nothing waits on another workgroup.  Device pointers; *bad and the rows are
+// valid once the caller has drained the stream.
+static_assert(ROOM_SOME == FIT_ROOM_SOME && ROOM_PARTITION == FIT_ROOM_PARTITION &&
+                  ROOM_LIMIT_TIME == FIT_ROOM_LIMIT_TIME && ROOM_LIMIT_CPUS == FIT_ROOM_LIMIT_CPUS &&
+                  ROOM_LIMIT_MEM == FIT_ROOM_LIMIT_MEM && ROOM_NO_NODES == FIT_ROOM_NO_NODES &&
+                  ROOM_NONE == FIT_ROOM_NONE,
+              "fit_device.h and fitgpu.h disagree");
+static_assert(FIT_ROOM_PARTITION == FIT_WHY_PARTITION && FIT_ROOM_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
+                  FIT_ROOM_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && FIT_ROOM_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
+                  FIT_ROOM_NO_NODES == FIT_WHY_NO_NODES,
+              "FIT_ROOM_1..5 are FIT_WHY_1..5");
+static_assert(sizeof(struct fit_room) == 40 && offsetof(struct fit_room, copies) == 16 &&
+                  offsetof(struct fit_room, best_node) == 24,
+              "fit_room is 40 bytes, copies at 16");
+static_assert(FIT_ROOM_UNBOUNDED == INT32_MAX, "FIT_ROOM_UNBOUNDED is INT32_MAX");
+
+int room_impl(fit_ctx* c, int32_t J, const JobCols& d, struct fit_room* out, int32_t* bad) {
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_room_classify(c->st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, J, out,
+                                        c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_room(c->st, c->rec.p, ec, d.cpu, d.mem, d.gpu, d.wall, d.part, J, c->jcomp.p, jl, live,
+                               explain_slices(J, c->cls_maxn, c->cus), out);
+        });
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -1468,6 +1501,7 @@ int query_device(fit_ctx* c, QueryBufs<Row>& Q, int32_t j, const JobCols& d, Row
 
 int bad_explain_job() { return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > %d", FIT_MAX_K); }
 int bad_when_job() { return fail(FIT_E_INVAL, "a job has a negative demand"); }
+int bad_room_job() { return fail(FIT_E_INVAL, "a job has a negative demand"); }
 
 int load_timeline_impl(fit_ctx* c, int32_t slots, int32_t slot_min, int64_t ne) {
     if (c->tlhdr.ensure(std::max(c->nn, 1)) ||
@@ -1809,6 +1843,27 @@ int fit_when_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->wh.ms < 0) return fail(FIT_E_STATE, "no fit_when_device yet");
     *ms = c->wh.ms;
+    return 0;
+}
+
+int fit_room(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* wall,
+             const uint16_t* part, struct fit_room* out) {
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_room", -1);
+    if (rc || j == 0) return rc;
+    return query_host(c, c->rm, j, cpu, mem, gpu, wall, part, nullptr, out, room_impl, bad_room_job);
+}
+
+int fit_room_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                    const int32_t* wall, const uint16_t* part, struct fit_room* out) {
+    const int rc = check_job_args(c, j, {cpu, mem, gpu, wall, part, out}, "fit_room", -1);
+    if (rc || j == 0) return rc;
+    return query_device(c, c->rm, j, {cpu, mem, gpu, wall, part, nullptr}, out, room_impl, bad_room_job);
+}
+
+int fit_room_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->rm.ms < 0) return fail(FIT_E_STATE, "no fit_room_device yet");
+    *ms = c->rm.ms;
     return 0;
 }
 

@@ -203,6 +203,24 @@ hipError_t launch_when(hipStream_t st, const TlHdr* hdr, const Seg* slab, const 
                        const uint16_t* jpart, int32_t nj, const int8_t* jcomp, const int32_t* jl,
                        const int32_t* live, int slices, void* out);
 
+// ---- fit_room (fit_room.hip) -------------------------------------------
+// The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
+enum RoomCode : int32_t {
+    ROOM_SOME = 0,
+    ROOM_PARTITION = 1,
+    ROOM_LIMIT_TIME = 2,
+    ROOM_LIMIT_CPUS = 3,
+    ROOM_LIMIT_MEM = 4,
+    ROOM_NO_NODES = 5,
+    ROOM_NONE = 6,
+};
+hipError_t launch_room_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                                int32_t nj, void* out, int8_t* jcomp, int32_t* bad);
+hipError_t launch_room(hipStream_t st, const NodeRec* rec, const ExplainComps& C, const int32_t* jcpu,
+                       const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                       int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* out);
+
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {
     TRIP_NONE = 0,

@@ -975,4 +975,48 @@ int fit_when_message(const fit_eta* e, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_room row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
+// with the same numbers and take its sentences.  No device, no context.
+int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen) {
+    if (!r || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    switch (r->code) {
+        case FIT_ROOM_PARTITION:
+        case FIT_ROOM_LIMIT_TIME:
+        case FIT_ROOM_LIMIT_CPUS:
+        case FIT_ROOM_LIMIT_MEM:
+        case FIT_ROOM_NO_NODES: {
+            fit_why w;
+            memset(&w, 0, sizeof w);
+            w.code = r->code;
+            return fit_why_message(&w, buf, buflen);
+        }
+        case FIT_ROOM_NONE: s = "no room now on any of " + std::to_string(r->members) + " nodes"; break;
+        case FIT_ROOM_SOME: {
+            const std::string on = std::to_string(r->nodes) + "/" + std::to_string(r->members) + " nodes";
+            if (r->best == FIT_ROOM_UNBOUNDED) {
+                s = "no resource demand: unlimited room on " + on;
+                break;
+            }
+            s = "room for " + std::to_string(r->copies) + " more on " + on + " (at most " + std::to_string(r->best) +
+                " on one node)";
+            const struct {
+                int32_t n;
+                const char* what;
+            } terms[] = {{r->by_gpu, "gpu on "}, {r->by_cpu, "cpu on "}, {r->by_mem, "memory on "}};
+            const char* sep = ": limited by ";
+            for (const auto& t : terms) {
+                if (t.n == 0) continue;
+                s += sep + std::string(t.what) + std::to_string(t.n);
+                sep = ", ";
+            }
+            break;
+        }
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 }  // extern "C"

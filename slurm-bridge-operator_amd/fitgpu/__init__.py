@@ -34,7 +34,9 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
                    FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy,
                    FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
-                   FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta)
+                   FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta,
+                   FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
+                   FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -48,6 +50,8 @@ __all__ = [
     "FIT_WHY_LIMIT_CPUS", "FIT_WHY_LIMIT_MEM", "FIT_WHY_NO_NODES", "FIT_WHY_RESOURCES",
     "when_message", "ETA_DTYPE", "FIT_ETA_NOW", "FIT_ETA_PARTITION", "FIT_ETA_LIMIT_TIME", "FIT_ETA_LIMIT_CPUS",
     "FIT_ETA_LIMIT_MEM", "FIT_ETA_NO_NODES", "FIT_ETA_LATER", "FIT_ETA_HORIZON",
+    "room_message", "ROOM_DTYPE", "FitRoom", "FIT_ROOM_SOME", "FIT_ROOM_PARTITION", "FIT_ROOM_LIMIT_TIME",
+    "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
 ]
 
 
@@ -365,6 +369,22 @@ def when_message(row) -> str:
     return buf.raw[:n].decode()
 
 
+# ---------------------------------------------------------------------------------- room
+# one fit_room row (include/fitgpu.h), 40 bytes with copies as int64 at offset 16: what Engine.room /
+# Admitter.room return
+ROOM_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.int32) for n, t in FitRoom._fields_])
+
+
+def room_message(row) -> str:
+    """A fit_room row (an element of a room() result, or any mapping / object with its fields) as
+    one line of text (fit_room_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    r = FitRoom(*(int(get(n)) for n, _ in FitRoom._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_room_message(C.byref(r), buf, len(buf)), "fit_room_message")
+    return buf.raw[:n].decode()
+
+
 # ------------------------------------------------------------------------------- engine
 def lock_dir() -> tuple[str, bool]:
     """fit_lock_dir: the directory of the per-GPU launch lock file and whether it is the shared
@@ -586,6 +606,31 @@ class Engine:
         check(lib().fit_when_ms(self._h, C.byref(ms)), "fit_when_ms")
         return ms.value
 
+    # ---- how many more copies of a job fit now ---------------------------
+    def room(self, jobs):
+        """Every job judged alone against the current node table (fit_room): a structured array of
+        ROOM_DTYPE rows (code, members, nodes, best, copies, best_node, by_gpu, by_cpu, by_mem).
+        Changes nothing; jobs.nodes_k plays no part (the row counts node shares)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        out = np.zeros(len(part), ROOM_DTYPE)
+        check(lib().fit_room(self._h, len(part), *[_ptr(c) for c in cols], _ptr(part), _ptr(out)), "fit_room")
+        return out
+
+    def room_device(self, cpu, mem, gpu, wall, part, out):
+        """All arguments torch tensors resident on this GPU; writes out (J rows of 40 bytes,
+        ROOM_DTYPE's layout, 8-byte aligned: an int64 tensor of J * 5 words will do).  Returns the
+        device time of its launches in ms (HIP events on the context's stream, fit_room_ms); 0.0
+        for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_room_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part), _ptr(out)),
+              "fit_room_device")
+        if j == 0:
+            return 0.0
+        ms = C.c_double()
+        check(lib().fit_room_ms(self._h, C.byref(ms)), "fit_room_ms")
+        return ms.value
+
     def read_timeline(self):
         """Dense [n, slots, 3] int32 (cpu, mem, gpu)."""
         c, m, g = (np.empty((self.n, self.slots), np.int32) for _ in range(3))
@@ -671,6 +716,16 @@ class Admitter:
         q = (FitAdmitReq * max(n, 1))(*[FitAdmitReq(*r) for r in reqs])
         out = np.zeros(n, WHY_DTYPE)
         check(self._call(lambda h: lib().fit_admitter_explain(h, q, n, _ptr(out))), "fit_admitter_explain")
+        return out
+
+    def room(self, reqs: list[tuple]):
+        """fit_admitter_room of (priority, cpu, mem, gpu, wall, part, k) requests against the table
+        the next batch would see, open reservations included: ROOM_DTYPE rows.  Priority and k are
+        ignored."""
+        n = len(reqs)
+        q = (FitAdmitReq * max(n, 1))(*[FitAdmitReq(*r) for r in reqs])
+        out = np.zeros(n, ROOM_DTYPE)
+        check(self._call(lambda h: lib().fit_admitter_room(h, q, n, _ptr(out))), "fit_admitter_room")
         return out
 
     def load_nodes(self, nodes):

@@ -42,6 +42,7 @@ EXPORTS = [
     "fit_admitter_script", "fit_set_max_array_size", "fit_release_events", "fit_set_watchdog_us",
     "fit_lock_dir", "fit_explain", "fit_explain_device", "fit_admitter_explain", "fit_why_message",
     "fit_explain_ms", "fit_when", "fit_when_device", "fit_when_ms", "fit_when_message",
+    "fit_room", "fit_room_device", "fit_room_ms", "fit_room_message", "fit_admitter_room",
 ]
 
 
@@ -106,6 +107,18 @@ FIT_ETA_LIMIT_MEM, FIT_ETA_NO_NODES, FIT_ETA_LATER, FIT_ETA_HORIZON = 4, 5, 6, 7
 
 class FitEta(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("code", "dur", "start", "node", "wait_min", "members", "hosts", "now")]
+
+
+# fit_room.code (include/fitgpu.h): 1-5 are FIT_WHY_*'s; precedence 1, 2, 3, 4, 5, 6, 0
+FIT_ROOM_SOME, FIT_ROOM_PARTITION, FIT_ROOM_LIMIT_TIME, FIT_ROOM_LIMIT_CPUS = 0, 1, 2, 3
+FIT_ROOM_LIMIT_MEM, FIT_ROOM_NO_NODES, FIT_ROOM_NONE = 4, 5, 6
+FIT_ROOM_UNBOUNDED = 2**31 - 1  # per of a feasible node for an all-zero demand
+
+
+class FitRoom(C.Structure):
+    _fields_ = [("code", C.c_int32), ("members", C.c_int32), ("nodes", C.c_int32), ("best", C.c_int32),
+                ("copies", C.c_int64), ("best_node", C.c_int32), ("by_gpu", C.c_int32), ("by_cpu", C.c_int32),
+                ("by_mem", C.c_int32)]
 
 
 FIT_TABLE_STATE = 1  # fit_node_table.flags: part_mask carries node State (include/fitgpu.h)
@@ -176,6 +189,11 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
         L.fit_when_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_when_message.argtypes = [C.POINTER(FitEta), C.c_char_p, i32]
+        for name in ("fit_room", "fit_room_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
+        L.fit_room_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_room_message.argtypes = [C.POINTER(FitRoom), C.c_char_p, i32]
+        L.fit_admitter_room.argtypes = [P, C.POINTER(FitAdmitReq), i32, P]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

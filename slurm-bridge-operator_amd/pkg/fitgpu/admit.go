@@ -161,6 +161,30 @@ func (ad *Admitter) Explain(ds []Demand) ([]Why, error) {
 	return out, nil
 }
 
+// Room counts, for each request, the further copies of it that fit the table the next batch would
+// see, open reservations included (fit_admitter_room).  Priority, flags and NodesK are ignored.
+// Safe for concurrent use; it does not queue behind the coalescer and reserves nothing.
+func (ad *Admitter) Room(ds []Demand) ([]Room, error) {
+	if len(ds) == 0 {
+		return nil, nil
+	}
+	reqs := make([]C.fit_admit_req, len(ds))
+	for i, d := range ds {
+		reqs[i] = cReq(d)
+	}
+	rows := make([]C.struct_fit_room, len(ds))
+	rc := C.fit_admitter_room(ad.a, &reqs[0], C.int32_t(len(ds)), &rows[0])
+	runtime.KeepAlive(ad)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Room, len(ds))
+	for i := range rows {
+		out[i] = goRoom(&rows[i])
+	}
+	return out, nil
+}
+
 // WhyMessage is the row as one line in kube-scheduler's FailedScheduling shape (fit_why_message:
 // "0/6273 nodes fit now (need 2): 5120 insufficient cpu, 73 insufficient memory"); "" for a row
 // with an unknown code.

@@ -412,6 +412,78 @@ func WhenMessage(t Eta) string {
 	return string(buf[:int(n)])
 }
 
+// Room codes (fit_room.code, include/fitgpu.h): how many more copies of a job fit now.
+// RoomPartition .. RoomNoNodes are WhyPartition .. WhyNoNodes.
+const (
+	RoomSome      = int32(C.FIT_ROOM_SOME)
+	RoomPartition = int32(C.FIT_ROOM_PARTITION)
+	RoomLimitTime = int32(C.FIT_ROOM_LIMIT_TIME)
+	RoomLimitCPUs = int32(C.FIT_ROOM_LIMIT_CPUS)
+	RoomLimitMem  = int32(C.FIT_ROOM_LIMIT_MEM)
+	RoomNoNodes   = int32(C.FIT_ROOM_NO_NODES)
+	RoomNone      = int32(C.FIT_ROOM_NONE)
+	RoomUnbounded = int32(C.FIT_ROOM_UNBOUNDED) // Best for a job that demands nothing
+)
+
+// Room is one fit_room row: the job judged alone against the current node table (DESIGN.md §2e).
+type Room struct {
+	Code     int32 // Room*
+	Members  int32 // schedulable nodes of the job's partition
+	Nodes    int32 // members the job fits now (Why.Fit)
+	Best     int32 // the most copies one node takes, 0 if none
+	Copies   int64 // copies over all members: Place of m one-node copies alone places min(m, Copies)
+	BestNode int32 // a node that takes Best copies, the lowest id on a tie; -1 if none
+	ByGPU    int32 // fitting members on which the GPUs run out first
+	ByCPU    int32 // ... the cpus
+	ByMem    int32 // ... the memory
+}
+
+func goRoom(r *C.struct_fit_room) Room {
+	return Room{Code: int32(r.code), Members: int32(r.members), Nodes: int32(r.nodes), Best: int32(r.best),
+		Copies: int64(r.copies), BestNode: int32(r.best_node), ByGPU: int32(r.by_gpu), ByCPU: int32(r.by_cpu),
+		ByMem: int32(r.by_mem)}
+}
+
+// Room gives every job, judged alone against the current node table, the number of further copies
+// of it that fit now and what limits them (fit_room); it changes nothing.  NodesK is not read: for
+// a k-node job the row counts node shares.
+func (e *Engine) Room(j Jobs) ([]Room, error) {
+	cnt := len(j.CPU)
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part)) {
+		return nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil
+	}
+	rows := make([]C.struct_fit_room, cnt)
+	rc := C.fit_room(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])), &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Room, cnt)
+	for i := range rows {
+		out[i] = goRoom(&rows[i])
+	}
+	return out, nil
+}
+
+// RoomMessage is the row as one line (fit_room_message: "room for 12 more on 3/40 nodes (at most 5
+// on one node): limited by gpu on 2, cpu on 1"); "" for a row with an unknown code.
+func RoomMessage(r Room) string {
+	c := C.struct_fit_room{code: C.int32_t(r.Code), members: C.int32_t(r.Members), nodes: C.int32_t(r.Nodes),
+		best: C.int32_t(r.Best), copies: C.int64_t(r.Copies), best_node: C.int32_t(r.BestNode),
+		by_gpu: C.int32_t(r.ByGPU), by_cpu: C.int32_t(r.ByCPU), by_mem: C.int32_t(r.ByMem)}
+	buf := make([]byte, 256)
+	n := C.fit_room_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
 // IngestNodes turns `scontrol show nodes` output into the engine's node table (Client.Nodes +
 // parseNode, pkg/slurm-agent/slurm.go:354-363 / parse.go:291-308, plus Gres/GresUsed, State,
 // Partitions and NodeName), partitions[p] = the partition of part_mask bit p.

@@ -197,7 +197,8 @@ func (f *FitAdmission) admit(pod *v1.Pod) (string, []int64, error) {
 // limit, or how many of the partition's nodes are short of cpus, memory, GPUs or walltime
 // (kube-scheduler's FailedScheduling text, which the pod lost when the fit moved here).  From an
 // Explain of the pod's first request (an array job's tasks are identical) against the table the
-// batch left.  The diagnosis never fails an admission: on an error it is logged and "" returned,
+// batch left; for an array job that fits task by task but not as a whole, how many of its tasks
+// fit (Room).  The diagnosis never fails an admission: on an error it is logged and "" returned,
 // so the caller's text is the old one.
 func (f *FitAdmission) why(pod *v1.Pod, ds []fitgpu.Demand) string {
 	if len(ds) == 0 {
@@ -210,8 +211,20 @@ func (f *FitAdmission) why(pod *v1.Pod, ds []fitgpu.Demand) string {
 	}
 	// a job can be unplaced in its batch and fit alone a moment later (a release in between, an
 	// array job whose tasks fit one by one but not together): "fits it now: 3/10 nodes fit now"
-	// would contradict itself, so that case keeps the old text; the pod is retried anyway
+	// would contradict itself, so that case keeps the old text — but for the array job, whose
+	// diagnosis is how many of its one-node tasks the table takes now (Room of the first request);
+	// the pod is retried anyway
 	if ws[0].Code == fitgpu.WhyFits {
+		if len(ds) > 1 && ds[0].NodesK <= 1 {
+			rs, err := f.adm.Room(ds[:1])
+			if err != nil || len(rs) == 0 {
+				klog.Warningf("fit: no room count for pod %s/%s: %v", pod.Namespace, pod.Name, err)
+				return ""
+			}
+			if rs[0].Copies < int64(len(ds)) {
+				return fmt.Sprintf(": room for %d of its %d array tasks now", rs[0].Copies, len(ds))
+			}
+		}
 		return ""
 	}
 	msg := fitgpu.WhyMessage(ws[0])
