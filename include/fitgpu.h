@@ -163,7 +163,9 @@ int fit_place_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t*
                      const int32_t* gpu, const int32_t* wall, const uint16_t* part,
                      const uint16_t* nodes_k, int32_t kmax, int32_t* out_node, fit_stats* stats);
 
-/* Current (post-placement) free columns, in node-id order.  Host pointers, n entries each. */
+/* Current (post-placement) free columns, in node-id order.  Host pointers, n entries each.
+ * A column value that was loaded negative (the engine's own row holds max(value, -1): no job fits
+ * either, so such a node never receives one) reads back exactly as it was loaded. */
 int fit_read_nodes(fit_ctx* ctx, int32_t* cpu_free, int32_t* mem_free, int32_t* gpu_free);
 /* Free capacity per partition (Σ over member nodes of the current free columns): the engine's
  * replacement for the allocation-blind sum of GetPartitionCapacity (node.go:183-190). */
@@ -239,6 +241,7 @@ int fit_why_message(const fit_why* w, char* buf, int32_t buflen);
  * [rel_off[x], rel_off[x+1]) with non-decreasing rel_slot (slot <= 0 = already free) and amounts
  * >= 0.  A node is usable for slots t < avail_min / slot_min.  Call after fit_load_nodes (which
  * drops the timeline); rel_off NULL = no releases.  Host pointers; rel_off has n+1 entries.
+ * At most 2^22 - 1 nodes with a partition bit (the backfill key's position field): FIT_E_INVAL.
  * The walltime source is the job's --time (pkg/slurm-bridge-operator/parse.go:84-91) and the
  * squeue EndTime of running jobs; the partition MaxTime check is parseResources' (parse.go:128-138). */
 int fit_load_timeline(fit_ctx* ctx, int32_t slots, int32_t slot_min, const int32_t* rel_off,

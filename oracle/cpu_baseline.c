@@ -120,6 +120,12 @@ typedef struct {
     const int32_t* id;
 } soa_t;
 
+/* A node field below -1 fits no demand (demands are >= 0), and neither does -1: the working copy
+ * holds max(field, -1), so that `field - demand` in the key loops cannot overflow int32 (INT32_MIN -
+ * demand would wrap to "fits").  A negative field is never chosen, hence never changed: the copy
+ * back keeps the caller's value for it. */
+static inline int32_t floor_m1(int32_t v) { return v < -1 ? -1 : v; }
+
 /* min key over positions [0, len) — branch-free so the loop vectorises */
 __attribute__((target_clones("avx512f", "avx2", "default")))
 static uint64_t scan_min(int32_t len, const int32_t* cf, const int32_t* mf, const int32_t* gf,
@@ -163,10 +169,10 @@ static void place_component(plain_job_t* T, int k, int64_t* placed, int64_t* eva
     const int32_t* id = C->nodes + nb;
     for (int32_t i = 0; i < len; i++) {
         const int32_t x = id[i];
-        cf[i] = T->cpu_free[x];
-        mf[i] = T->mem_free[x];
-        gf[i] = T->gpu_free[x];
-        av[i] = T->avail[x];
+        cf[i] = floor_m1(T->cpu_free[x]);
+        mf[i] = floor_m1(T->mem_free[x]);
+        gf[i] = floor_m1(T->gpu_free[x]);
+        av[i] = floor_m1(T->avail[x]);
         mk[i] = T->mask[x];
     }
     /* position of a node id inside the component (ids ascend) */
@@ -191,9 +197,9 @@ static void place_component(plain_job_t* T, int k, int64_t* placed, int64_t* eva
     }
     for (int32_t i = 0; i < len; i++) {
         const int32_t x = id[i];
-        T->cpu_free[x] = cf[i];
-        T->mem_free[x] = mf[i];
-        T->gpu_free[x] = gf[i];
+        if (cf[i] >= 0) T->cpu_free[x] = cf[i];
+        if (mf[i] >= 0) T->mem_free[x] = mf[i];
+        if (gf[i] >= 0) T->gpu_free[x] = gf[i];
     }
     free(cf);
     free(mk);
@@ -328,10 +334,10 @@ static void place_component_k(k_job_t* K, int k, int64_t* placed, int64_t* evals
     const int32_t* id = C->nodes + nb;
     for (int32_t i = 0; i < len; i++) {
         const int32_t x = id[i];
-        cf[i] = T->cpu_free[x];
-        mf[i] = T->mem_free[x];
-        gf[i] = T->gpu_free[x];
-        av[i] = T->avail[x];
+        cf[i] = floor_m1(T->cpu_free[x]);
+        mf[i] = floor_m1(T->mem_free[x]);
+        gf[i] = floor_m1(T->gpu_free[x]);
+        av[i] = floor_m1(T->avail[x]);
         mk[i] = T->mask[x];
     }
     for (int32_t t = C->jb[k]; t < C->jb[k + 1]; t++) {
@@ -370,9 +376,9 @@ static void place_component_k(k_job_t* K, int k, int64_t* placed, int64_t* evals
     }
     for (int32_t i = 0; i < len; i++) {
         const int32_t x = id[i];
-        T->cpu_free[x] = cf[i];
-        T->mem_free[x] = mf[i];
-        T->gpu_free[x] = gf[i];
+        if (cf[i] >= 0) T->cpu_free[x] = cf[i];
+        if (mf[i] >= 0) T->mem_free[x] = mf[i];
+        if (gf[i] >= 0) T->gpu_free[x] = gf[i];
     }
     free(cf);
     free(mk);

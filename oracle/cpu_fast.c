@@ -114,6 +114,11 @@ static void spin_wait(spin_barrier* b, int* local_sense) {
     }
 }
 
+/* The working copy of a node field is max(field, -1) (soa_load): nothing fits either, and `field -
+ * demand` below cannot overflow int32 (INT32_MIN - demand would wrap to "fits").  soa_store keeps
+ * the caller's value for a negative field, which no job can have changed. */
+static inline int32_t floor_m1(int32_t v) { return v < -1 ? -1 : v; }
+
 /* SoA key of one position (SPEC §2 key; position = node id) */
 static inline uint64_t soa_key(int32_t cf, int32_t mf, int32_t gf, int32_t av, uint32_t mk, int32_t id,
                                int32_t c, int32_t m, int32_t g, int32_t w, uint32_t pbit) {
@@ -158,10 +163,10 @@ static int soa_load(soa_t* s, const groups_t* G, int k, const int32_t* cpu_free,
     for (int32_t i = 0; i < len; i++) {
         const int32_t x = G->nodes[nb + i];
         s->id[i] = x;
-        s->cf[i] = cpu_free[x];
-        s->mf[i] = mem_free[x];
-        s->gf[i] = gpu_free[x];
-        s->av[i] = avail[x];
+        s->cf[i] = floor_m1(cpu_free[x]);
+        s->mf[i] = floor_m1(mem_free[x]);
+        s->gf[i] = floor_m1(gpu_free[x]);
+        s->av[i] = floor_m1(avail[x]);
         s->mk[i] = mask[x];
     }
     return 0;
@@ -169,9 +174,9 @@ static int soa_load(soa_t* s, const groups_t* G, int k, const int32_t* cpu_free,
 
 static void soa_store(soa_t* s, int32_t* cpu_free, int32_t* mem_free, int32_t* gpu_free) {
     for (int32_t i = 0; i < s->len; i++) {
-        cpu_free[s->id[i]] = s->cf[i];
-        mem_free[s->id[i]] = s->mf[i];
-        gpu_free[s->id[i]] = s->gf[i];
+        if (s->cf[i] >= 0) cpu_free[s->id[i]] = s->cf[i];
+        if (s->mf[i] >= 0) mem_free[s->id[i]] = s->mf[i];
+        if (s->gf[i] >= 0) gpu_free[s->id[i]] = s->gf[i];
     }
     free(s->cf);
     free(s->mk);

@@ -1530,9 +1530,11 @@ int check_timeline_args(fit_ctx* c, int32_t slots, int32_t slot_min) {
     if (slots < 1 || slots > TL_MAX_SLOTS || slot_min < 1)
         return fail(FIT_E_INVAL, "horizon of %d slots x %d min (1..%d slots)", slots, slot_min,
                     TL_MAX_SLOTS);
-    if (c->nn > (int32_t)TL_POS_MASK + 1)
-        return fail(FIT_E_INVAL, "%d nodes exceed the timeline key's %d-bit position", c->nn,
-                    TL_POS_BITS);
+    // positions stop one short of the field's range: start 1023, an all-capped score and position
+    // 2^22 - 1 would make a feasible key equal to KEY_INF ("no start")
+    if (c->nn > (int32_t)TL_POS_MASK)
+        return fail(FIT_E_INVAL, "%d nodes: the timeline key's %d-bit position holds at most %d", c->nn,
+                    TL_POS_BITS, (int32_t)TL_POS_MASK);
     return 0;
 }
 

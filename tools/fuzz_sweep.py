@@ -6,6 +6,11 @@ the oracle (placements, final node state, counters); and the backfill cases of t
 exits non-zero at the first mismatch, naming seed and engine.
 
     python tools/fuzz_sweep.py 1000 1500 > gpurun_out/<tag>_fuzz_sweep.txt
+
+With --edges the cases come from tests/_edge_cases.py's edge_case instead (score caps, scores of 0 and
+0xFFFFFFFF, int32 extremes; family = seed % 4), the same engines and comparisons:
+
+    python tools/fuzz_sweep.py 0 400 --edges
 """
 import os
 import sys
@@ -18,14 +23,16 @@ import numpy as np  # noqa: E402
 
 from fitgpu import Engine  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
+from _edge_cases import edge_case  # noqa: E402
 from test_fuzz_gpu import random_case  # noqa: E402
 
 
-def main(lo: int, hi: int) -> int:
+def main(lo: int, hi: int, edges: bool = False) -> int:
+    draw = edge_case if edges else random_case
     t0 = time.time()
     cases = jobs_total = multi = 0
     for seed in range(lo, hi):
-        nodes, jobs, parts, kmax = random_case(seed)
+        nodes, jobs, parts, kmax = draw(seed)
         ref, rst, rfin = po.ref_place(nodes, jobs, parts, kmax=kmax)
         for eng in ("persistent", "rounds", "direct", "class"):
             os.environ["FIT_ENGINE"] = eng
@@ -41,7 +48,7 @@ def main(lo: int, hi: int) -> int:
                 print(f"MISMATCH seed {seed} engine {eng} kmax {kmax}: {where}", flush=True)
                 return 1
             cases += 1
-        nodes, tl, tjobs, parts = random_case(seed, timeline=True)
+        nodes, tl, tjobs, parts = draw(seed, timeline=True)
         rn, rs, rst, rfin = po.ref_place_tl(nodes, tl, tjobs, parts)
         live = nodes.part_mask != 0
         for eng in ("persistent", "rounds"):
@@ -69,4 +76,5 @@ def main(lo: int, hi: int) -> int:
 
 
 if __name__ == "__main__":
-    sys.exit(main(int(sys.argv[1]), int(sys.argv[2])))
+    args = [a for a in sys.argv[1:] if a != "--edges"]
+    sys.exit(main(int(args[0]), int(args[1]), edges="--edges" in sys.argv[1:]))
