@@ -339,6 +339,62 @@ int fit_when_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_when_message(const fit_eta* e, char* buf, int32_t buflen);
 
+/* ---- when a multi-node job can start ---------------------------------------
+ * fit_when for jobs of nodes_k nodes: the earliest slot at which need = max(nodes_k, 1) DISTINCT
+ * member nodes all hold the demand over the same d slots, and the need best-fitting of the nodes
+ * free there.  Judged alone against the current timeline, read-only, as fit_when.  With S_n the set
+ * of slots s (s + d <= slots) from which node n holds (cpu, mem, gpu) on every slot of [s, s + d),
+ * cnt(s) is the number of members with s in S_n.  The common start can be later than every node's
+ * own earliest start: the k-th smallest of fit_when's per-node starts is not the answer.  For
+ * need == 1 start, the node and the counters are fit_when's.  The codes are FIT_ETA_*, numbers and
+ * precedence unchanged; FIT_ETA_HORIZON here means no s has cnt(s) >= need (hosts < need and
+ * dur > slots are two ways to get there).  For codes 1-4 every field but code, dur and need is 0,
+ * with start = wait_min = -1.  One 40-byte row per job. */
+typedef struct {
+    int32_t code;      /* FIT_ETA_*                                                            */
+    int32_t dur;       /* max(1, ceil(wall / slot_min)) slots; set for every code             */
+    int32_t need;      /* nodes_k, 0 treated as 1; set for every code                         */
+    int32_t start;     /* the smallest s with cnt(s) >= need, -1 if none                      */
+    int32_t wait_min;  /* start * slot_min, saturated at INT32_MAX; -1 if none                */
+    int32_t members;   /* nodes with the job's partition bit set                              */
+    int32_t hosts;     /* members that have any start inside the horizon                      */
+    int32_t now;       /* cnt(0): members that hold the demand from slot 0                    */
+    int32_t ready;     /* cnt(start): members that hold it from `start`; 0 if none            */
+    int32_t reserved;  /* 0                                                                   */
+} fit_eta_k;
+/* Host pointers; nodes_k may be NULL (= all 1).  out_node has j * kmax entries: when the code is
+ * FIT_ETA_NOW or FIT_ETA_LATER, out_node[j * kmax + i], i < need, are the need smallest (score,
+ * node id) among the members that hold the demand from `start`, in that order — the score is
+ * fit_place's packing of the window minima minus the demand; every other entry is -1.  j == 0
+ * returns 0 whatever the pointers are.  FIT_E_INVAL: NULL ctx / arrays, j < 0, kmax < 1 or kmax >
+ * FIT_MAX_K, any max(nodes_k, 1) > kmax, any negative demand (the whole call fails).  FIT_E_STATE:
+ * before fit_load_nodes; without a timeline loaded; on a context created with world > 1 or
+ * FIT_FLAG_COLLECTIVES.  Bounded launches per chunk of 16,384 jobs, no persistent grid: the call
+ * neither takes the per-GPU persistent-launch lock nor needs the watchdog. */
+int fit_when_k(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+               const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+               fit_eta_k* out, int32_t* out_node);
+/* Same with device pointers (inputs resident in HBM, rows and nodes written in HBM). */
+int fit_when_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                      const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                      fit_eta_k* out, int32_t* out_node);
+/* Diagnostic, for measurement only (tools/when_k_bench.py): device time of the last successful
+ * fit_when_k_device on this context, in milliseconds (HIP events on the context's own stream around
+ * its launches).  FIT_E_STATE when there has been none. */
+int fit_when_k_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text, NUL-terminated into buf.  Host only: no device, no context.
+ * Returns the length written (without the NUL), or FIT_E_INVAL: NULL arguments, an unknown code,
+ * or a buffer too small for the text and its NUL (256 bytes always suffice).  The exact texts,
+ * <x> a decimal field of the row:
+ *   FIT_ETA_NOW         "can start now on <need> of <ready>/<members> nodes"
+ *   FIT_ETA_LATER       "earliest start in <wait_min> min (slot <start>) on <need> of
+ *                        <ready>/<members> nodes, <now> free now"   — on one line
+ *   FIT_ETA_HORIZON     "no start inside the horizon for <need> nodes at once: <hosts>/<members>
+ *                        nodes can run it"   — on one line
+ *   FIT_ETA_NO_NODES / LIMIT_TIME / LIMIT_CPUS / LIMIT_MEM / PARTITION: fit_why_message's texts of
+ *                       the codes with the same numbers, verbatim */
+int fit_when_k_message(const fit_eta_k* e, char* buf, int32_t buflen);
+
 /* ---- how many more copies of a job fit now ---------------------------------
  * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a
  * partition takes of one shape, the resource that runs out first: fit_room judges each of J jobs

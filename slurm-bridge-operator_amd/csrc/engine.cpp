@@ -317,6 +317,12 @@ struct fit_ctx : CtxHandles {
     QueryBufs<fit_why> ex;
     QueryBufs<fit_eta> wh;
     QueryBufs<struct fit_room> rm;
+    // fit_when_k: its rows, the node lists of the host entry point (device, pinned), and the
+    // scratch of one job chunk — difference arrays and per-slice keys
+    QueryBufs<fit_eta_k> wk;
+    DBuf<int32_t> wk_node, wk_diff;
+    HBuf<int32_t> h_wk_node;
+    DBuf<unsigned long long> wk_top;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1403,6 +1409,63 @@ int room_impl(fit_ctx* c, int32_t J, const JobCols& d, struct fit_room* out, int
         });
 }
 
+// --------------------------------------------------------------------------- fit_when_k
+// classify the batch, (more than a group of jobs on several components: the
+// jobs in component order), then per chunk of WHENK_CHUNK jobs count (difference arrays), pick the
+// start, pick the nodes, finalise.  query_impl's sequence with a chunk loop in place of its one
+// walk, hence written out here.  Bounded launches on the context's stream, no
+// synchronisation between chunks — the stream orders their use of the one scratch — and nothing
+// waits on another workgroup.  Device pointers; *bad, the rows and the nodes are valid once the
+// caller has drained the stream.
+static_assert(sizeof(fit_eta_k) == 40 && offsetof(fit_eta_k, members) == 20 && offsetof(fit_eta_k, reserved) == 36,
+              "fit_eta_k is 40 bytes");
+
+// node slices per job, from the sweep of DESIGN.md §3.14: about four count workgroups (one per
+// WHENK_GROUP jobs and slice) per CU from a short batch, two slices when the jobs alone fill the
+// chip, and at least one workgroup's worth of nodes (256) per slice
+int whenk_slices(int32_t nj, int32_t maxn, int cus) {
+    const int64_t groups = ((int64_t)std::max(nj, 1) + WHENK_GROUP - 1) / WHENK_GROUP;
+    const int64_t want = std::max<int64_t>(2, ((int64_t)cus * 4 + groups - 1) / groups);
+    const int64_t fit = ((int64_t)maxn + 255) / 256;
+    return (int)std::max<int64_t>(1, std::min<int64_t>({want, fit, (int64_t)WHENK_MAX_SLICES}));
+}
+
+int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k* out, int32_t* out_node,
+                int32_t* bad) {
+    hipStream_t st = c->st;
+    const int C = c->ncomp, H = c->tl_slots;
+    const int32_t chunk = std::min<int32_t>(J, WHENK_CHUNK);
+    const int S = whenk_slices(chunk, c->cls_maxn, c->cus);
+    if (c->jcomp.ensure(std::max(J, 1)) || c->wk_diff.ensure((size_t)chunk * (H + 1)) ||
+        c->wk_top.ensure((size_t)chunk * S * WHENK_KEYS))
+        return FIT_E_OOM;
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    HIP_TRY(launch_whenk_classify(st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, J,
+                                  c->tl_slot_min, out, out_node, c->jcomp.p, bad));
+    if (C < 1) return 0;  // no node in any partition: every row is final
+    // a count workgroup walks the nodes once for WHENK_GROUP jobs of one component: order the jobs
+    // by component when a group would mix them (query_impl's job list)
+    const int32_t *jl = nullptr, *live = nullptr;
+    if (J > WHENK_GROUP && C > 1) {
+        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
+            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
+            return FIT_E_OOM;
+        int32_t* g = c->jls.p + joblists_scratch_ints(J);
+        int32_t* jbd = g + 2;
+        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
+        jl = c->jl.p;
+        live = jbd + C;  // jobs that have a component
+    }
+    ExplainComps ec;
+    ec.ncomp = C;
+    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+    for (int32_t t0 = 0; t0 < J; t0 += WHENK_CHUNK)
+        HIP_TRY(launch_whenk_chunk(st, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, d.cpu, d.mem, d.gpu, d.wall,
+                                   d.part, t0, std::min<int32_t>(J - t0, WHENK_CHUNK), J, kmax, c->jcomp.p, jl, live, S,
+                                   c->wk_diff.p, c->wk_top.p, out, out_node));
+    return 0;
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -1845,6 +1908,60 @@ int fit_when_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->wh.ms < 0) return fail(FIT_E_STATE, "no fit_when_device yet");
     *ms = c->wh.ms;
+    return 0;
+}
+
+// fit_when_k / fit_when_k_device: fit_when's tests, then kmax (nodes_k against kmax is the
+// device's flag word)
+static int check_when_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_when_k", 1);
+    if (rc) return rc;
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+static int bad_when_k_job() { return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > kmax"); }
+
+int fit_when_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+               const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax, fit_eta_k* out,
+               int32_t* out_node) {
+    const int rc = check_when_k_args(c, j, {cpu, mem, gpu, wall, part, out, out_node}, kmax);
+    if (rc || j == 0) return rc;
+    // the node lists come back into pinned memory behind the launches, ahead of query_host's copy of
+    // the rows and its synchronisation; they reach out_node only when the call succeeds
+    const size_t nn = (size_t)j * kmax;
+    if (c->wk_node.ensure(nn) || c->h_wk_node.ensure(nn)) return FIT_E_OOM;
+    const int r = query_host(
+        c, c->wk, j, cpu, mem, gpu, wall, part, nk, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_eta_k* rows, int32_t* bad) {
+            const int e = when_k_impl(x, n, d, kmax, rows, x->wk_node.p, bad);
+            if (e) return e;
+            HIP_TRY(hipMemcpyAsync(x->h_wk_node.p, x->wk_node.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, x->st));
+            return 0;
+        },
+        bad_when_k_job);
+    if (r) return r;
+    memcpy(out_node, c->h_wk_node.p, sizeof(int32_t) * nn);
+    return 0;
+}
+
+int fit_when_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                      const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax, fit_eta_k* out,
+                      int32_t* out_node) {
+    const int rc = check_when_k_args(c, j, {cpu, mem, gpu, wall, part, out, out_node}, kmax);
+    if (rc || j == 0) return rc;
+    return query_device(
+        c, c->wk, j, {cpu, mem, gpu, wall, part, nk}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_eta_k* rows, int32_t* bad) {
+            return when_k_impl(x, n, d, kmax, rows, out_node, bad);
+        },
+        bad_when_k_job);
+}
+
+int fit_when_k_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->wk.ms < 0) return fail(FIT_E_STATE, "no fit_when_k_device yet");
+    *ms = c->wk.ms;
     return 0;
 }
 

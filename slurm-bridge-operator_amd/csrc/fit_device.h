@@ -203,6 +203,23 @@ hipError_t launch_when(hipStream_t st, const TlHdr* hdr, const Seg* slab, const 
                        const uint16_t* jpart, int32_t nj, const int8_t* jcomp, const int32_t* jl,
                        const int32_t* live, int slices, void* out);
 
+// ---- fit_when_k (fit_when_k.hip) ---------------------------------------
+// The codes are EtaCode's.  Scratch per chunk of jobs: a difference array of H + 1 words per job
+// (64 MiB at WHENK_CHUNK jobs and H = 1,024) and WHENK_KEYS keys per (job, node slice).
+constexpr int WHENK_CHUNK = 16384;    // jobs per count / pick / nodes / final sequence
+constexpr int WHENK_GROUP = 8;       // jobs per k_whenk_count workgroup: 8 difference arrays in LDS (32.8 KB)
+constexpr int WHENK_KEYS = 8;         // keys a node slice hands on per job (= FIT_KMAX)
+constexpr int WHENK_MAX_SLICES = 16;  // node slices per job: k_whenk_final merges slices * WHENK_KEYS keys per job
+hipError_t launch_whenk_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                 const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                 const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t nj,
+                                 int32_t slot_min, void* out, int32_t* out_node, int8_t* jcomp, int32_t* bad);
+hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                              const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
+                              int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
+                              int32_t* diff, unsigned long long* top, void* out, int32_t* out_node);
+
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
 enum RoomCode : int32_t {

@@ -1,0 +1,438 @@
+// fit_when_k.hip — earliest common start of each multi-node job on the timeline: per job, the
+// smallest slot at which `need` distinct member nodes all hold the demand for the job's d slots,
+// and the `need` best-fitting of the nodes free there (include/fitgpu.h fit_when_k; DESIGN.md §2f,
+// §3.14).  Read-only: the run lists are only loaded.  gfx950.
+//
+// Ordinary bounded launches, whatever J and N are; the middle four run per chunk of jobs so that
+// the scratch stays bounded:
+//   k_whenk_classify : per job, the partition-limit code (k_when_classify's rule), `dur`, `need`,
+//                      the row's counters zeroed and the job's component
+//   k_whenk_count    : one workgroup per (group of 8 jobs, node slice), threads = nodes.  A thread
+//                      loads its node's WHOLE run list once and steps the group's jobs over it:
+//                      for every maximal feasible stretch [a, b) of at least d slots of a job, +1
+//                      at a and -1 at b - d + 1 of that job's difference array in LDS (H + 1
+//                      words each, 32.8 KB for the group).  The workgroup flushes the non-zero
+//                      words to the jobs' arrays in HBM with returnless integer atomics,
+//                      lane-contiguous, and adds `members` / `hosts`.  Above 8 jobs on several
+//                      components the jobs come in component order (launch_joblists), so that a
+//                      group shares its nodes.
+//   k_whenk_pick     : one wave per job: the prefix sum of the differences, 64 slots per step, is
+//                      cnt(s); the first s with cnt >= need is the start.  Stores start, ready, now.
+//   k_whenk_nodes    : one workgroup per (job with a start, node slice), threads = nodes: the one
+//                      window [start, start + d) on the run list gives feasibility and the minima,
+//                      hence score << TL_POS_BITS | pos.  A thread keeps its 8 smallest keys sorted
+//                      in registers; the workgroup extracts its `need` smallest through an LDS
+//                      64-bit min per round and stores them per (job, slice).
+//   k_whenk_final    : one wave per job: the `need` smallest of the slices' keys -> out_node
+//                      (TlHdr::orig, key order), wait_min and the code.
+// Cross-workgroup traffic is integer atomicAdd (commutative) or disjoint stores, so rows are exact
+// and reproducible.  No cross-workgroup wait of any kind: no watchdog, no persistent-launch lock.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "fit_device.h"
+#include "fit_tl_walk.h"
+
+namespace fitgpu {
+
+constexpr int WK_THREADS = 256;  // threads (= nodes in flight) per count / nodes workgroup
+constexpr int WK_GROUP = WHENK_GROUP;  // jobs a count workgroup steps over the runs it loads
+
+// fit_eta_k as include/fitgpu.h declares it
+struct EtaKRow {
+    int32_t code, dur, need, start, wait_min, members, hosts, now, ready, reserved;
+};
+static_assert(sizeof(EtaKRow) == 40 && offsetof(EtaKRow, members) == 20, "fit_eta_k is 40 bytes");
+static_assert(WHENK_KEYS == FIT_KMAX, "a slice keeps one key per node of the widest job");
+static_assert(WHENK_MAX_SLICES * WHENK_KEYS <= 128, "k_whenk_final holds two keys per lane");
+static_assert(TL_HEAD % 4 == 0 && TL_MAX_SLOTS % 4 == 0, "the walks load four Seg at a time inside a slab row");
+
+__global__ __launch_bounds__(256) void k_whenk_classify(
+    const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
+    const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk,
+    int32_t kmax, int32_t nj, const int32_t* __restrict__ ptab /* [4][32]: time, cpus, mem, comp */, int32_t np,
+    int32_t slot_min, EtaKRow* __restrict__ out, int8_t* __restrict__ jcomp, int32_t* __restrict__ bad) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nj) return;
+    const int p = jpart[q];
+    const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
+    const int32_t need = max(jk ? (int32_t)jk[q] : 1, 1);
+    int code = ETA_NOW, comp = -1;
+    if (p >= np) {
+        code = ETA_PARTITION;
+    } else {
+        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
+        if (mt >= 0 && w > mt) code = ETA_LIMIT_TIME;
+        else if (mc >= 0 && c > mc) code = ETA_LIMIT_CPUS;
+        else if (mm >= 0 && m > mm) code = ETA_LIMIT_MEM;
+        else comp = ptab[96 + p];  // -1: no node carries the partition's bit
+    }
+    if (c < 0 || m < 0 || g < 0 || w < 0 || need > kmax) {  // the whole call fails (FIT_E_INVAL)
+        comp = -1;
+        atomicOr(bad, 1);
+    }
+    // wall -> slots occupied: ceil(wall / slot_min), at least 1 (k_when_classify's rule)
+    const int64_t dw = ((int64_t)max(w, 0) + slot_min - 1) / slot_min;
+    EtaKRow r;
+    // a job without a component has no member node and is in no job list: its row is final here
+    r.code = code == ETA_NOW && comp < 0 ? ETA_NO_NODES : code;
+    r.dur = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));
+    r.need = need;
+    r.start = r.wait_min = -1;
+    r.members = r.hosts = r.now = r.ready = r.reserved = 0;
+    out[q] = r;
+    jcomp[q] = (int8_t)comp;
+}
+
+// The node slice [a, b) of component `comp` for slice blockIdx.y; false: nothing to do.
+__device__ __forceinline__ bool whenk_slice(const ExplainComps& C, int comp, int& a, int& b) {
+    if (comp < 0 || comp >= C.ncomp) return false;
+    const int nb = C.nb[comp], ne = C.nb[comp + 1];
+    const int per = (ne - nb + (int)gridDim.y - 1) / (int)gridDim.y;
+    a = min(ne, nb + (int)blockIdx.y * per);
+    b = min(ne, a + per);
+    return a < b;
+}
+
+// Position t of the batch -> job: the component-ordered list's (jl, *live of them) or the caller's
+// order; -1 behind the end.
+__device__ __forceinline__ int whenk_job(int t, const int32_t* __restrict__ jl, const int32_t* __restrict__ live,
+                                         int32_t njobs) {
+    const int nlive = jl ? min(*live, njobs) : njobs;
+    if (t >= nlive) return -1;
+    const int q = jl ? jl[t] : t;
+    return q >= 0 && q < njobs ? q : -1;
+}
+
+// grid (groups of WK_GROUP positions of the chunk [t0, t0 + nj), node slices); diff: the chunk's
+// difference arrays, H + 1 words per position, zero before the launch.  A thread loads a node's
+// runs once and steps all jobs of the group over them: their demands are block-uniform, the
+// stretch state is one register per job.  With the jobs in component order a group is one
+// component but for a seam; a group passes once over each distinct component of its jobs, each job
+// judging only its own.
+__global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
+    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, ExplainComps C, int32_t H, int32_t slot_min,
+    int32_t t0, int32_t nj, const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t njobs,
+    const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
+    const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart, const int8_t* __restrict__ jcomp,
+    EtaKRow* __restrict__ out, int32_t* __restrict__ diff) {
+    __shared__ int32_t ld[WK_GROUP][TL_MAX_SLOTS + 1];
+    __shared__ int32_t cnt[WK_GROUP][2];  // members, hosts
+    const int tb = blockIdx.x * WK_GROUP;  // chunk-local position of the group's first job
+    int32_t q[WK_GROUP], comp[WK_GROUP], cpu[WK_GROUP], mem[WK_GROUP], gpu[WK_GROUP], d[WK_GROUP];
+    uint32_t pbit[WK_GROUP];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int g = 0; g < WK_GROUP; ++g) {
+        const int qq = tb + g < nj ? whenk_job(t0 + tb + g, jl, live, njobs) : -1;
+        int c = qq >= 0 ? (int)jcomp[qq] : -1;
+        if (c >= C.ncomp) c = -1;
+        const bool on = c >= 0;
+        q[g] = qq;
+        comp[g] = c;
+        cpu[g] = on ? jcpu[qq] : 0;
+        mem[g] = on ? jmem[qq] : 0;
+        gpu[g] = on ? jgpu[qq] : 0;
+        const int64_t dw = on ? ((int64_t)max(jwall[qq], 0) + slot_min - 1) / slot_min : 1;
+        d[g] = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));  // k_whenk_classify's `dur`
+        pbit[g] = on ? 1u << (jpart[qq] & 31) : 0u;
+        valid |= on ? 1u << g : 0u;
+    }
+    if (!valid) return;  // block-uniform
+    for (int i = threadIdx.x; i < WK_GROUP * (TL_MAX_SLOTS + 1); i += WK_THREADS) (&ld[0][0])[i] = 0;
+    if (threadIdx.x < WK_GROUP * 2) (&cnt[0][0])[threadIdx.x] = 0;
+    __syncthreads();
+    int32_t members[WK_GROUP], hosts[WK_GROUP];
+#pragma unroll
+    for (int g = 0; g < WK_GROUP; ++g) members[g] = hosts[g] = 0;
+
+    uint32_t rem = valid;
+    while (rem) {  // block-uniform: one pass per distinct component among the group's jobs
+        const int first = __builtin_ctz(rem);
+        int c = -1;
+#pragma unroll
+        for (int g = 0; g < WK_GROUP; ++g) c = g == first ? comp[g] : c;
+        uint32_t act = 0;
+#pragma unroll
+        for (int g = 0; g < WK_GROUP; ++g) act |= ((valid >> g) & 1u) && comp[g] == c ? 1u << g : 0u;
+        rem &= ~act;
+        int a, b;
+        if (!whenk_slice(C, c, a, b)) continue;
+        for (int x = a + threadIdx.x; x < b; x += WK_THREADS) {
+            const TlHdr h = hdr[x];
+            // members; the header's column ceilings and d <= H reject a node without a walk (when_node's rule)
+            uint32_t lv = 0;
+#pragma unroll
+            for (int g = 0; g < WK_GROUP; ++g) {
+                const bool mb = ((act >> g) & 1u) && (h.mask & pbit[g]);
+                members[g] += mb;
+                lv |= mb && d[g] <= H && cpu[g] <= h.cpu && mem[g] <= h.mem && gpu[g] <= h.gpu ? 1u << g : 0u;
+            }
+            if (!lv) continue;
+            const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
+            const int cn = min(h.cnt, TL_MAX_SLOTS);
+            int32_t s0 = 0;         // start of the current run
+            int32_t ra[WK_GROUP];   // per job, start of the current feasible stretch (-1: none)
+#pragma unroll
+            for (int g = 0; g < WK_GROUP; ++g) ra[g] = -1;
+            uint32_t any = 0;
+            // one run [s0, e) with (rc, rm, rg) free, vr false behind the last run: per job, the run holds
+            // the demand or the job's stretch ends at s0
+            auto step = [&](bool vr, int32_t rc, int32_t rm, int32_t rg, int32_t e) {
+#pragma unroll
+                for (int g = 0; g < WK_GROUP; ++g) {
+                    const bool f = vr & (bool)((lv >> g) & 1u) & (rc >= cpu[g]) & (rm >= mem[g]) & (rg >= gpu[g]);
+                    if (!f && ra[g] >= 0) {
+                        if (s0 - ra[g] >= d[g]) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
+                            atomicAdd(&ld[g][ra[g]], 1);
+                            atomicAdd(&ld[g][s0 - d[g] + 1], -1);
+                            any |= 1u << g;
+                        }
+                        ra[g] = -1;
+                    }
+                    if (f && ra[g] < 0 && s0 < H) ra[g] = s0;
+                }
+                s0 = min(max(e, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
+            };
+#pragma unroll
+            for (int i = 0; i < TL_HEAD; ++i)
+                if (i < cn) step(true, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, h.head[i].end);
+            for (int i = TL_HEAD; i < cn; i += 4) {  // four Seg per wait, as when_node
+                Seg r4[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (i + k < cn) step(true, r4[k].cpu, r4[k].mem, r4[k].gpu, r4[k].end);
+            }
+            step(false, 0, 0, 0, H);
+#pragma unroll
+            for (int g = 0; g < WK_GROUP; ++g) hosts[g] += (any >> g) & 1u;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < WK_GROUP; ++g) {
+        if (members[g]) atomicAdd(&cnt[g][0], members[g]);
+        if (hosts[g]) atomicAdd(&cnt[g][1], hosts[g]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < WK_GROUP; ++g) {
+        if (!((valid >> g) & 1u)) continue;  // block-uniform
+        int32_t* df = diff + (int64_t)(tb + g) * (H + 1);
+        for (int i = threadIdx.x; i <= H; i += WK_THREADS) {
+            const int32_t v = ld[g][i];
+            if (v) atomicAdd(&df[i], v);
+        }
+        if (threadIdx.x == 0 && cnt[g][0]) atomicAdd(&out[q[g]].members, cnt[g][0]);
+        if (threadIdx.x == 1 && cnt[g][1]) atomicAdd(&out[q[g]].hosts, cnt[g][1]);
+    }
+}
+
+// One wave per job, 4 jobs per workgroup: cnt(s) is the prefix sum of the differences.
+__global__ __launch_bounds__(256) void k_whenk_pick(const int32_t* __restrict__ diff, int32_t H, int32_t t0,
+                                                    int32_t nj, const int32_t* __restrict__ jl,
+                                                    const int32_t* __restrict__ live, int32_t njobs,
+                                                    const int8_t* __restrict__ jcomp, EtaKRow* __restrict__ out) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= nj) return;  // wave-uniform
+    const int q = whenk_job(t0 + t, jl, live, njobs);
+    if (q < 0 || jcomp[q] < 0) return;  // rejected, or no member at all: start stays -1
+    const int32_t need = out[q].need, d = out[q].dur;
+    if (d > H) return;
+    const int32_t* df = diff + (int64_t)t * (H + 1);
+    int32_t carry = 0, start = -1, ready = 0, now = 0;
+    for (int base = 0; base < H; base += 64) {  // starts lie in [0, H - d]; word H only takes -1s
+        const int s = base + lane;
+        int32_t v = s < H ? df[s] : 0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t u = __shfl_up(v, off);
+            if (lane >= off) v += u;
+        }
+        v += carry;  // cnt(s)
+        if (base == 0) now = __shfl(v, 0);
+        const uint64_t hit = __ballot(s < H && v >= need);
+        if (hit) {
+            const int first = __builtin_ctzll(hit);
+            start = base + first;
+            ready = __shfl(v, first);
+            break;
+        }
+        carry = __shfl(v, 63);
+    }
+    if (lane == 0) {
+        out[q].now = now;
+        out[q].start = start;
+        out[q].ready = ready;
+    }
+}
+
+// grid (positions of the chunk, node slices); top: WHENK_KEYS keys per (position, slice), KEY_INF
+// before the launch.
+__global__ __launch_bounds__(WK_THREADS) void k_whenk_nodes(
+    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, ExplainComps C, int32_t H, int32_t t0,
+    const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t njobs,
+    const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
+    const uint16_t* __restrict__ jpart, const int8_t* __restrict__ jcomp, const EtaKRow* __restrict__ out,
+    unsigned long long* __restrict__ top) {
+    __shared__ unsigned long long best;
+    const int q = whenk_job(t0 + blockIdx.x, jl, live, njobs);
+    if (q < 0) return;  // block-uniform
+    const int32_t start = out[q].start;
+    int a, b;
+    if (start < 0 || !whenk_slice(C, jcomp[q], a, b)) return;  // block-uniform
+    const int32_t cpu = jcpu[q], mem = jmem[q], gpu = jgpu[q];
+    const int32_t d = out[q].dur, need = min(out[q].need, WHENK_KEYS);
+    const int32_t stop = start + d;  // <= H: k_whenk_pick found the start among s + d <= H
+    const uint32_t pbit = 1u << (jpart[q] & 31);
+    uint64_t key[WHENK_KEYS];
+#pragma unroll
+    for (int i = 0; i < WHENK_KEYS; ++i) key[i] = KEY_INF;
+    for (int x = a + threadIdx.x; x < b; x += WK_THREADS) {
+        const TlHdr h = hdr[x];
+        if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
+        const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
+        const int cn = min(h.cnt, TL_MAX_SLOTS);
+        int32_t mc = 0x7fffffff, mm = 0x7fffffff, mg = 0x7fffffff;
+        bool ok = true, closed = false;  // closed: the runs seen cover the window
+        // runs end in increasing order and the walk stops at the first that reaches `stop`, so a run
+        // meets the window exactly when it ends behind `start`
+        auto run = [&](const Seg& r) {
+            if (r.end <= start) return;
+            ok = (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
+            mc = min(mc, r.cpu);
+            mm = min(mm, r.mem);
+            mg = min(mg, r.gpu);
+            closed = r.end >= stop;
+        };
+#pragma unroll
+        for (int i = 0; i < TL_HEAD; ++i)
+            if (i < cn && ok && !closed) run(h.head[i]);
+        for (int i = TL_HEAD; i < cn && ok && !closed; i += 4) {  // four Seg per wait, as when_node
+            Seg r4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i + k < cn && ok && !closed) run(r4[k]);
+        }
+        if (!ok || !closed) continue;
+        uint64_t k = tl_key(0, mc, mm, mg, cpu, mem, gpu, (uint32_t)x);
+#pragma unroll
+        for (int i = 0; i < WHENK_KEYS; ++i) {  // sorted insert: k carries the larger one on
+            const uint64_t lo = min(k, key[i]);
+            k = max(k, key[i]);
+            key[i] = lo;
+        }
+    }
+    // the workgroup's `need` smallest: per round the minimum of the threads' heads; keys are
+    // distinct (the position), so exactly one thread owns it and moves its list up
+    unsigned long long* o = top + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * WHENK_KEYS;
+    for (int r = 0; r < need; ++r) {
+        if (threadIdx.x == 0) best = KEY_INF;
+        __syncthreads();
+        if (key[0] != KEY_INF) atomicMin(&best, (unsigned long long)key[0]);
+        __syncthreads();
+        const uint64_t w = best;
+        __syncthreads();  // every thread has read `best` before the next round resets it
+        if (w == KEY_INF) break;  // block-uniform
+        if (key[0] == w) {
+#pragma unroll
+            for (int i = 0; i + 1 < WHENK_KEYS; ++i) key[i] = key[i + 1];
+            key[WHENK_KEYS - 1] = KEY_INF;
+            o[r] = w;
+        }
+    }
+}
+
+// One wave per position, 4 per workgroup: the wave holds the slices' keys, two per lane, and takes
+// the `need` smallest in `need` rounds of a wave minimum; lane 0 writes the row.
+__global__ __launch_bounds__(256) void k_whenk_final(EtaKRow* __restrict__ out, int32_t t0, int32_t nj,
+                                                     const int32_t* __restrict__ jl,
+                                                     const int32_t* __restrict__ live, int32_t njobs,
+                                                     const unsigned long long* __restrict__ top, int slices,
+                                                     const TlHdr* __restrict__ hdr, int32_t slot_min, int32_t kmax,
+                                                     int32_t* __restrict__ out_node) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= nj) return;  // wave-uniform, as every return below
+    const int q = whenk_job(t0 + t, jl, live, njobs);
+    if (q < 0) return;
+    EtaKRow r = out[q];
+    if (r.code != ETA_NOW) return;  // limit codes and jobs without a component: final since k_whenk_classify
+    if (r.members == 0) {
+        r.code = ETA_NO_NODES;
+    } else if (r.start < 0) {
+        r.code = ETA_HORIZON;
+        r.ready = 0;
+    } else {
+        r.wait_min = (int32_t)min<int64_t>((int64_t)r.start * slot_min, 0x7fffffff);
+        r.code = r.start > 0 ? ETA_LATER : ETA_NOW;
+        const unsigned long long* k = top + (int64_t)t * slices * WHENK_KEYS;
+        const int n = slices * WHENK_KEYS;  // <= 128 = two per lane
+        uint64_t k0 = lane < n ? k[lane] : KEY_INF, k1 = 64 + lane < n ? k[64 + lane] : KEY_INF;
+        for (int i = 0; i < r.need && i < kmax; ++i) {
+            uint64_t m = min(k0, k1);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t lo = __shfl_xor((uint32_t)m, off), hi = __shfl_xor((uint32_t)(m >> 32), off);
+                m = min(m, ((uint64_t)hi << 32) | lo);
+            }
+            if (m == KEY_INF) break;  // cannot happen: ready >= need nodes passed k_whenk_nodes
+            if (lane == 0) out_node[(int64_t)q * kmax + i] = hdr[(uint32_t)m & TL_POS_MASK].orig;
+            k0 = k0 == m ? KEY_INF : k0;  // keys are distinct: one lane gives it up
+            k1 = k1 == m ? KEY_INF : k1;
+        }
+    }
+    if (lane == 0) out[q] = r;
+}
+
+// The query on stream st.  Classify the whole batch first (`out`: nj rows of 40 B; out_node:
+// nj * kmax words, all -1 afterwards; *bad: 1 for a negative demand or nodes_k > kmax) ...
+hipError_t launch_whenk_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                 const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                 const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t nj,
+                                 int32_t slot_min, void* out, int32_t* out_node, int8_t* jcomp, int32_t* bad) {
+    if (nj <= 0) return hipSuccess;
+    if (slot_min < 1 || kmax < 1 || kmax > FIT_KMAX) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(out_node, 0xff, sizeof(int32_t) * (size_t)nj * kmax, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_whenk_classify, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jpart, jk,
+                       kmax, nj, ptab, np, slot_min, static_cast<EtaKRow*>(out), jcomp, bad);
+    return hipGetLastError();
+}
+
+// ... then, per chunk of at most WHENK_CHUNK positions [t0, t0 + nj) of the batch: count, pick, nodes,
+// finalise.  jl / live: the component-ordered job list and its length on the device (njobs jobs in
+// all), or nullptr for the caller's order.  diff: nj * (H + 1) words and top: nj * slices *
+// WHENK_KEYS keys of scratch, reused by the next chunk on the same stream.
+hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                              const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
+                              int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
+                              int32_t* diff, unsigned long long* top, void* out, int32_t* out_node) {
+    if (nj <= 0) return hipSuccess;
+    if (C.ncomp < 1 || C.ncomp > 32 || slices < 1 || slices > WHENK_MAX_SLICES || nj > WHENK_CHUNK || H < 1 ||
+        H > TL_MAX_SLOTS || slot_min < 1 || kmax < 1 || kmax > FIT_KMAX || t0 < 0 || t0 + nj > njobs)
+        return hipErrorInvalidValue;
+    EtaKRow* o = static_cast<EtaKRow*>(out);
+    hipError_t e = hipMemsetAsync(diff, 0, sizeof(int32_t) * (size_t)nj * (H + 1), st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(top, 0xff, sizeof(unsigned long long) * (size_t)nj * slices * WHENK_KEYS, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_whenk_count, dim3((nj + WK_GROUP - 1) / WK_GROUP, slices), dim3(WK_THREADS), 0, st, hdr, slab,
+                       C, H, slot_min, t0, nj, jl, live, njobs, jcpu, jmem, jgpu, jwall, jpart, jcomp, o, diff);
+    hipLaunchKernelGGL(k_whenk_pick, dim3((nj + 3) / 4), dim3(256), 0, st, diff, H, t0, nj, jl, live, njobs, jcomp, o);
+    hipLaunchKernelGGL(k_whenk_nodes, dim3(nj, slices), dim3(WK_THREADS), 0, st, hdr, slab, C, H, t0, jl, live, njobs,
+                       jcpu, jmem, jgpu, jpart, jcomp, o, top);
+    hipLaunchKernelGGL(k_whenk_final, dim3((nj + 3) / 4), dim3(256), 0, st, o, t0, nj, jl, live, njobs, top, slices,
+                       hdr, slot_min, kmax, out_node);
+    return hipGetLastError();
+}
+
+}  // namespace fitgpu

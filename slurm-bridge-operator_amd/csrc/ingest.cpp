@@ -975,6 +975,40 @@ int fit_when_message(const fit_eta* e, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_eta_k row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
+// with the same numbers and take its sentences.  No device, no context.
+int fit_when_k_message(const fit_eta_k* e, char* buf, int32_t buflen) {
+    if (!e || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    const std::string of = std::to_string(e->need) + " of " + std::to_string(e->ready) + "/" +
+                           std::to_string(e->members) + " nodes";
+    switch (e->code) {
+        case FIT_ETA_PARTITION:
+        case FIT_ETA_LIMIT_TIME:
+        case FIT_ETA_LIMIT_CPUS:
+        case FIT_ETA_LIMIT_MEM:
+        case FIT_ETA_NO_NODES: {
+            fit_why w;
+            memset(&w, 0, sizeof w);
+            w.code = e->code;
+            return fit_why_message(&w, buf, buflen);
+        }
+        case FIT_ETA_NOW: s = "can start now on " + of; break;
+        case FIT_ETA_LATER:
+            s = "earliest start in " + std::to_string(e->wait_min) + " min (slot " + std::to_string(e->start) +
+                ") on " + of + ", " + std::to_string(e->now) + " free now";
+            break;
+        case FIT_ETA_HORIZON:
+            s = "no start inside the horizon for " + std::to_string(e->need) + " nodes at once: " +
+                std::to_string(e->hosts) + "/" + std::to_string(e->members) + " nodes can run it";
+            break;
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 // A fit_room row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
 // with the same numbers and take its sentences.  No device, no context.
 int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen) {

@@ -34,7 +34,7 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
                    FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy,
                    FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
-                   FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta,
+                   FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta, FitEtaK, FIT_MAX_K,
                    FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
                    FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom)
 
@@ -50,6 +50,7 @@ __all__ = [
     "FIT_WHY_LIMIT_CPUS", "FIT_WHY_LIMIT_MEM", "FIT_WHY_NO_NODES", "FIT_WHY_RESOURCES",
     "when_message", "ETA_DTYPE", "FIT_ETA_NOW", "FIT_ETA_PARTITION", "FIT_ETA_LIMIT_TIME", "FIT_ETA_LIMIT_CPUS",
     "FIT_ETA_LIMIT_MEM", "FIT_ETA_NO_NODES", "FIT_ETA_LATER", "FIT_ETA_HORIZON",
+    "when_k_message", "ETA_K_DTYPE", "FitEtaK", "FIT_MAX_K",
     "room_message", "ROOM_DTYPE", "FitRoom", "FIT_ROOM_SOME", "FIT_ROOM_PARTITION", "FIT_ROOM_LIMIT_TIME",
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
 ]
@@ -369,6 +370,21 @@ def when_message(row) -> str:
     return buf.raw[:n].decode()
 
 
+# -------------------------------------------------------------------------------- when_k
+# one fit_eta_k row (include/fitgpu.h), 40 bytes: what Engine.when_k returns
+ETA_K_DTYPE = np.dtype([(n, np.int32) for n, _ in FitEtaK._fields_])
+
+
+def when_k_message(row) -> str:
+    """A fit_eta_k row (an element of a when_k() result, or any mapping / object with its fields)
+    as one line of text (fit_when_k_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    e = FitEtaK(*(int(get(n)) for n, _ in FitEtaK._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_when_k_message(C.byref(e), buf, len(buf)), "fit_when_k_message")
+    return buf.raw[:n].decode()
+
+
 # ---------------------------------------------------------------------------------- room
 # one fit_room row (include/fitgpu.h), 40 bytes with copies as int64 at offset 16: what Engine.room /
 # Admitter.room return
@@ -604,6 +620,40 @@ class Engine:
             return 0.0
         ms = C.c_double()
         check(lib().fit_when_ms(self._h, C.byref(ms)), "fit_when_ms")
+        return ms.value
+
+    # ---- when a multi-node job can start ---------------------------------
+    def when_k(self, jobs, kmax: int | None = None):
+        """Every job judged alone against the current timeline as a job of jobs.nodes_k nodes
+        (fit_when_k): (rows, nodes) — a structured array of ETA_K_DTYPE rows (code, dur, need,
+        start, wait_min, members, hosts, now, ready, reserved) and nodes[J, kmax], the job's nodes
+        in key order for a NOW / LATER row, -1 elsewhere.  kmax None: the largest nodes_k of the
+        batch (at least 1).  Changes nothing."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        j = len(part)
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j else 1
+        out = np.zeros(j, ETA_K_DTYPE)
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        check(lib().fit_when_k(self._h, j, *[_ptr(c) for c in cols], _ptr(part), _ptr(k), int(kmax), _ptr(out),
+                               _ptr(nodes)), "fit_when_k")
+        return out, nodes
+
+    def when_k_device(self, cpu, mem, gpu, wall, part, nodes_k, out, out_node, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1); writes
+        out (J rows of 10 int32, the fields of ETA_K_DTYPE in order) and out_node (J * kmax int32).
+        Returns the device time of its launches in ms (HIP events on the context's stream,
+        fit_when_k_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_when_k_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                      _ptr(nodes_k) if nodes_k is not None else None, int(kmax), _ptr(out),
+                                      _ptr(out_node)), "fit_when_k_device")
+        if j == 0:
+            return 0.0
+        ms = C.c_double()
+        check(lib().fit_when_k_ms(self._h, C.byref(ms)), "fit_when_k_ms")
         return ms.value
 
     # ---- how many more copies of a job fit now (DESIGN.md §2e) ---------------------------

@@ -43,6 +43,7 @@ EXPORTS = [
     "fit_lock_dir", "fit_explain", "fit_explain_device", "fit_admitter_explain", "fit_why_message",
     "fit_explain_ms", "fit_when", "fit_when_device", "fit_when_ms", "fit_when_message",
     "fit_room", "fit_room_device", "fit_room_ms", "fit_room_message", "fit_admitter_room",
+    "fit_when_k", "fit_when_k_device", "fit_when_k_ms", "fit_when_k_message",
 ]
 
 
@@ -107,6 +108,11 @@ FIT_ETA_LIMIT_MEM, FIT_ETA_NO_NODES, FIT_ETA_LATER, FIT_ETA_HORIZON = 4, 5, 6, 7
 
 class FitEta(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("code", "dur", "start", "node", "wait_min", "members", "hosts", "now")]
+
+
+class FitEtaK(C.Structure):  # fit_eta_k: the codes are FIT_ETA_*
+    _fields_ = [(n, C.c_int32) for n in ("code", "dur", "need", "start", "wait_min", "members", "hosts", "now",
+                                         "ready", "reserved")]
 
 
 # fit_room.code (include/fitgpu.h): 1-5 are FIT_WHY_*'s; precedence 1, 2, 3, 4, 5, 6, 0
@@ -189,6 +195,10 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
         L.fit_when_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_when_message.argtypes = [C.POINTER(FitEta), C.c_char_p, i32]
+        for name in ("fit_when_k", "fit_when_k_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, P]
+        L.fit_when_k_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_when_k_message.argtypes = [C.POINTER(FitEtaK), C.c_char_p, i32]
         for name in ("fit_room", "fit_room_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
         L.fit_room_ms.argtypes = [P, C.POINTER(C.c_double)]
