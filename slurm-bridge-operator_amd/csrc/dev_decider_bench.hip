@@ -9,14 +9,19 @@ __global__ __launch_bounds__(64) void k_dec_bench(int w, int32_t* out, unsigned 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MwShared* S = reinterpret_cast<MwShared*>(smem);
     const int lane = threadIdx.x;
-    // eight records: 8 clean items each with distinct positions, demand 1 cpu
+    // eight records (snapshot v = 1): 8 items each with distinct positions, each the dirty row of
+    // its own slot (version 0: not stale until the decider rewrites the row), demand 1 cpu
+    mw_reset_items(S, threadIdx.x);
+    __syncthreads();
     for (int r = 0; r < MW_R; ++r) {
         if (lane == 0) {
-            S->rec[r].h = MwHdr{0u, 0, MW_M, r, 1, 1, 0, 0, 1u, 0u, KEY_INF};
+            S->rec[r].h = MwHdr{0u, 1, MW_M, r, 1, 1, 0, 0, 1u, 0u, KEY_INF};
         }
         if (lane < MW_M) {
-            S->rec[r].it[lane] = MwItem{(uint32_t)(r * MW_M + lane), (uint32_t)(lane + 1), r * MW_M + lane,
-                                        r * MW_M + lane, 1000000, 1000000, 0, 0, 1u, 0u, 0u, 0u};
+            const int s = r * MW_M + lane;
+            S->rec[r].it[lane] = MwItem{(uint32_t)s, (uint32_t)(lane + 1), s, s, 1000000, 1000000, 0, 0, 1u,
+                                        mw_lds_addr(&S->rows[s].ver), 0xffffffffu, 1u};
+            S->rows[s] = MwRow{1000000, 1000000, 0, 0, 1u, (uint32_t)s, s, 0};
         }
     }
     for (int i = lane; i < 64; i += 64) S->bitmap[i] = 0u;

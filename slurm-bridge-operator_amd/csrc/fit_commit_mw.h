@@ -17,6 +17,14 @@
 // row or bitmap word the helper read after the snapshot: any node changed after v is in the live
 // ring, so a torn or newer read of it only produces an item the decider drops.
 //
+// How an item is found stale.  "Its node is in the live ring" is "its node was written by a job in
+// [v, t)", and the shared state already says so in one LDS word per item, which the helper names
+// in the item (MwItem::chk_*): a clean item passed the helper's bitmap test, so its node's bit is
+// set now exactly when a job in [v, t) dirtied it; a dirty item's row carries `ver`, the last job
+// that created or changed it, and the item is stale exactly when ver >= v.  Both words are written
+// by the decider alone (its bookkeeping, in issue order before its next read), so the probe
+// crosses no wave.
+//
 // "Jobs" above are the window's LIVE jobs (round 3): a job that no node fits at the round's start
 // is unplaced whatever the decisions before it, so the helpers skip it (per-tile feasibility
 // masks from the scan, mw_skip_live) and record i, ring lane i & 7 and the snapshot counts all
@@ -28,8 +36,10 @@
 // ≈ 20-36, v_readlane → v_writelane ≈ 8.6, one LDS round trip ≈ 50-64.  So the decider's job
 // step is straight-line VALU with ONE exception branch per job (record not ready, B exceeded,
 // dirty set full, end of window), the written ring lives in lanes 0..7 (slot = job & 7, a
-// compile-time lane in the 8-way unrolled loop), item staleness is a lane-parallel XOR against
-// the ring rotated with DPP row_ror, the minimum over ring rows and items is three 64-bit DPP
+// compile-time lane in the 8-way unrolled loop), item staleness is one ds_read_b32 per lane at an
+// address the helper precomputed, issued at the top of the step and consumed after the ring
+// rows' keys (its round trip is covered; the DPP compare against the rotated ring it replaced
+// was 21 more instructions per job), the minimum over ring rows and items is three 64-bit DPP
 // steps over 8 lanes, and the next job's record is read while this one is decided.  The
 // decision's bookkeeping (dirty row, bitmap bit, placement) is issued by the decider itself as
 // fire-and-forget LDS writes.
@@ -72,14 +82,21 @@ static_assert(MW_EPL <= 2, "at most two candidate entries per lane");
 struct alignas(16) MwRow {  // dirty row, current state
     int32_t cpu, mem, gpu, avail;
     uint32_t mask, pos;
-    int32_t orig, ver;  // ver: last job (window index) that created or changed it
+    int32_t orig, ver;  // ver: last job (record index) that created or changed it; read back by
+                        // the decider's staleness probe of a dirty item
 };
 
-struct alignas(16) MwItem {  // 48 B; the decider reads the first 36
+struct alignas(16) MwItem {  // 48 B, read whole by the decider (three 16-B reads)
     uint32_t pos, score;  // key = score << 32 | pos
     int32_t tag, orig;    // tag: dirty slot (>= 0) or -1 (a clean candidate; row below)
     int32_t cpu, mem, gpu, avail;
-    uint32_t mask, pad0, pad1, pad2;
+    uint32_t mask;
+    // the staleness probe: the item is stale iff (LDS word at chk_addr & chk_mask) >= chk_thr.
+    //   clean item: its node's bitmap word, mask = thr = the node's bit (set by a fresh placement)
+    //   dirty item: &rows[tag].ver, mask = ~0, thr = the record's snapshot v (ver >= 0 always)
+    // chk_addr always lies inside MwShared: commit_window_mw points every item at MwShared::pad
+    // before the window starts, and only helpers write items after that.
+    uint32_t chk_addr, chk_mask, chk_thr;
 };
 
 struct alignas(16) MwHdr {
@@ -275,6 +292,12 @@ __device__ __forceinline__ T* lds_opaque(T* p) {
     uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p;
     asm volatile("" : "+s"(a));
     return (T*)(__attribute__((address_space(3))) T*)(uintptr_t)a;
+}
+
+// the 32-bit LDS address of an object in shared memory (what a ds_* instruction takes)
+template <class T>
+__device__ __forceinline__ uint32_t mw_lds_addr(T* p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p;
 }
 
 // The plan copied into SGPRs: an out-of-line function receives it through a generic pointer, and
@@ -716,17 +739,23 @@ __device__ __forceinline__ uint32_t wave_min32_all(uint32_t v) {
            the LDS, which the decider shares) */                                               \
         _Pragma("unroll") for (int e = 0; e < MW_EPL; ++e) {                                   \
             const uint32_t ix_ = (sel_ >> (4 * e)) & 15u;                                      \
-            if (ix_)                                                                           \
+            if (ix_) { /* probe: the node's bitmap bit */                                      \
+                const uint32_t rel_ = (uint32_t)x0[e] - (uint32_t)P.nb;                        \
+                const uint32_t bit_ = 1u << (rel_ & 31u);                                      \
                 R_->it[ix_ - 1u] = MwItem{(uint32_t)x0[e], (uint32_t)(x0[e] >> 32), -1,        \
                                           ro[A][e], rc[A][e], rm[A][e], rg[A][e], ra[A][e],    \
-                                          rk[A][e], 0u, 0u, 0u};                               \
+                                          rk[A][e], mw_lds_addr(&S->bitmap[rel_ >> 5]), bit_,  \
+                                          bit_};                                               \
+            }                                                                                  \
         }                                                                                      \
         _Pragma("unroll") for (int u = 0; u < UPL_MW; ++u) {                                   \
             const uint32_t ix_ = (sel_ >> (4 * (MW_EPL + u))) & 15u;                           \
-            if (ix_)                                                                           \
+            if (ix_) /* probe: the row's version against the snapshot */                       \
                 R_->it[ix_ - 1u] = MwItem{(uint32_t)xd[u], (uint32_t)(xd[u] >> 32),            \
                                           u * 64 + lane, wr_[u].orig, wr_[u].cpu, wr_[u].mem,  \
-                                          wr_[u].gpu, wr_[u].avail, wr_[u].mask, 0u, 0u, 0u};  \
+                                          wr_[u].gpu, wr_[u].avail, wr_[u].mask,               \
+                                          mw_lds_addr(&S->rows[u * 64 + lane].ver),            \
+                                          0xffffffffu, v_};                                    \
         }                                                                                      \
         if (lane == 0) {                                                                       \
             *reinterpret_cast<v4i32*>(&R_->h.cpu) = v4i32{J_.cpu, J_.mem, J_.gpu, J_.wall};    \
@@ -843,8 +872,7 @@ struct MwRing {
 typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 struct MwRecRegs {  // one record as this lane sees it: header (every lane) and item lane & 7
     v4u32 h0, h1, h2;  // {ready, v, n, q}, {cpu, mem, gpu, wall}, {pbit, -, B lo, B hi}
-    v4u32 i0, i1;      // {pos, score, tag, orig}, {cpu, mem, gpu, avail}
-    uint32_t i2;       // mask
+    v4u32 i0, i1, i2;  // {pos, score, tag, orig}, {cpu, mem, gpu, avail}, {mask, chk_addr, chk_mask, chk_thr}
 };
 
 struct MwDec {
@@ -882,7 +910,24 @@ __device__ __forceinline__ void mw_read_rec(const MwRec* R, int i8, MwRecRegs& x
     x.h2 = hp[2];
     x.i0 = ip[0];
     x.i1 = ip[1];
-    x.i2 = ((const __attribute__((address_space(3))) uint32_t*)ip)[8];
+    x.i2 = ip[2];
+}
+
+// Before a window starts (all threads of the block, ahead of its first barrier): the staleness
+// probe of every item of every record is pointed at MwShared::pad (one 16-B store per item: its
+// last 16 B, {mask, chk_addr, chk_mask, chk_thr}).  The decider issues an item's probe before it
+// knows that the record is complete or that the lane holds one of its n items; such an item is
+// this one or a helper's earlier one, so the read never leaves MwShared.  chk_addr is one aligned
+// 32-bit word, so a read that races a helper's store sees the old address or the new one, never
+// a mix; the mask and threshold read beside it may belong to the other item, but a record read
+// before its ready word is read again, and that first decision is dropped.  The rest of such an
+// item is never used (lane >= n, or the re-read), so it is left as it is.
+__device__ __forceinline__ void mw_reset_items(MwShared* S, unsigned tid) {
+    static_assert(sizeof(MwItem) == 48 && offsetof(MwItem, mask) == 32, "the probe is the last 16 B");
+    static_assert((MW_M & (MW_M - 1)) == 0, "item index by shift and mask");
+    const uint32_t sink = mw_lds_addr(&S->pad[0]);
+    for (unsigned i = tid; i < MW_R * MW_M; i += blockDim.x)
+        *reinterpret_cast<v4u32*>(&S->rec[i / MW_M].it[i % MW_M].mask) = v4u32{0u, sink, 0u, 0u};
 }
 
 // One job of the decider: job D.t with record `cur` (its data read after an acquire of the ready
@@ -928,22 +973,21 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
                       jw = (int32_t)x.h1.w;
         const uint32_t jp = x.h2.x;
         const uint64_t B = ((uint64_t)x.h2.w << 32) | x.h2.z;
+        // item staleness: was its node written by a job in [v, t)?  The helper left the LDS word
+        // that answers it (MwItem::chk_*): a clean item's bitmap word — its bit is set by the
+        // fresh placement that dirtied the node after the snapshot — or a dirty item's row
+        // version.  Both are written by this wave only (the bookkeeping of the jobs before t, in
+        // issue order before this read).  Issued here, consumed after the ring rows' keys.
+        // In bounds even when record t is not complete yet: chk_addr is a single aligned word,
+        // the window's initial one or a helper's, never torn (mw_reset_items).
+        const uint32_t pv = *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)x.i2.y;
         // live ring rows at their current state
         const bool live = R.b.w >= v;
         const uint64_t rk0 = mw_key(R.a.x, R.a.y, R.a.z, R.a.w, (uint32_t)R.b.x, (uint32_t)R.b.y,
                                     jc, jm, jg, jw, jp);
         const uint64_t rkey = live ? rk0 : KEY_INF;
         const uint32_t ip = x.i0.x;
-        // item staleness: its node is in the live ring.  Lanes 8..15 take a copy of the ring
-        // (row_ror:8), so row_ror:k, k = 0..7, shows lane i < 8 every ring entry once.
-        const uint32_t P0 = live ? (uint32_t)R.b.y : 0xffffffffu;  // positions are < 2^29
-        const uint32_t P8 = dpp32<0x128>(P0);
-        const uint32_t P2 = (lane & 8) ? P8 : P0;
-        const uint32_t d0 = ip ^ P2, d1 = dpp_ror_xor<1, true>(P2, ip),
-                       d2 = dpp_ror_xor<2, false>(P2, ip), d3 = dpp_ror_xor<3, false>(P2, ip),
-                       d4 = dpp_ror_xor<4, false>(P2, ip), d5 = dpp_ror_xor<5, false>(P2, ip),
-                       d6 = dpp_ror_xor<6, false>(P2, ip), d7 = dpp_ror_xor<7, false>(P2, ip);
-        const bool stale = min(min(min(d0, d1), min(d2, d3)), min(min(d4, d5), min(d6, d7))) == 0u;
+        const bool stale = (pv & x.i2.z) >= x.i2.w;
         const uint64_t ik0 = ((uint64_t)x.i0.y << 32) | ip;
         const uint64_t ikey = (lane < n && !stale) ? ik0 : KEY_INF;
         const bool tr = rkey < ikey;  // this lane's ring row beats its item
@@ -953,7 +997,7 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         d.sm = (tr ? R.a.y : (int32_t)x.i1.y) - jm;
         d.sg = (tr ? R.a.z : (int32_t)x.i1.z) - jg;
         d.sa = tr ? R.a.w : (int32_t)x.i1.w;
-        d.sk = tr ? R.b.x : (int32_t)x.i2;
+        d.sk = tr ? R.b.x : (int32_t)x.i2.x;
         d.so = tr ? R.b.z : (int32_t)x.i0.w;
         d.ss = tr ? R.slot : (int32_t)x.i0.z;
         const uint64_t best = min8_2pass(cand);
@@ -1041,7 +1085,7 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         typedef __attribute__((address_space(3))) MwRow* LRow;
         const uint32_t ra = (uint32_t)(uintptr_t)(LRow)&S->rows[slot];
         const uint32_t rel = (uint32_t)pos - (uint32_t)P.nb;
-        const uint32_t ba = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)&S->bitmap[rel >> 5];
+        const uint32_t ba = mw_lds_addr(&S->bitmap[rel >> 5]);
         const uint32_t bv = fresh ? 1u << (rel & 31) : 0u;
         const uint32_t pl = (uint32_t)rfl(placed ? 1 : 0);
         const uint64_t m = ((uint64_t)(uint32_t)rfl((int32_t)(pl << E)) |
@@ -1165,6 +1209,7 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
     const int nwords = (P.ne - P.nb + 31) >> 5;
     for (int i = threadIdx.x; i < nwords; i += MW_WAVES * 64) S->bitmap[i] = 0u;
     if (threadIdx.x < MW_R) S->rec[threadIdx.x].h.ready = 0u;
+    mw_reset_items(S, threadIdx.x);
     if (threadIdx.x == 0) {
         S->dn = 0ull;
         S->halt = 0u;
