@@ -105,6 +105,7 @@ typedef struct {
                            /* 2: direct small placement (k_small, <= FIT_SMALL_DIRECT jobs);         */
                            /* 3: demand-class engine (k_class: by default when the live jobs are at  */
                            /*    least half multi-node; FIT_CLASS=1 / 0 forces it on / off)          */
+                           /* 4: multi-node backfill (fit_place_tl_k: one workgroup per component)   */
     int32_t reserved;
     double ms_arb_wait;    /* host time waiting for the device's persistent-launch lock: one   */
                            /* persistent launch per GPU at a time, across contexts and processes */
@@ -256,7 +257,8 @@ int fit_load_timeline_device(fit_ctx* ctx, int32_t slots, int32_t slot_min,
  * earliest start slot at which its demand fits for ceil(wall / slot_min) consecutive slots, best
  * fit among the nodes with that start; the reservation is committed and later
  * jobs see it.  out_node[j]: node id, FIT_UNPLACED (no start inside the horizon) or FIT_REJECTED;
- * out_start[j]: start slot, -1 when not placed.  Host pointers. */
+ * out_start[j]: start slot, -1 when not placed.  Host pointers.  Jobs of several nodes on the
+ * timeline: fit_place_tl_k below. */
 int fit_place_tl(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem,
                  const int32_t* gpu, const int32_t* wall, const uint16_t* part, int32_t* out_node,
                  int32_t* out_start, fit_stats* stats);
@@ -394,6 +396,41 @@ int fit_when_k_ms(fit_ctx* ctx, double* ms);
  *   FIT_ETA_NO_NODES / LIMIT_TIME / LIMIT_CPUS / LIMIT_MEM / PARTITION: fit_why_message's texts of
  *                       the codes with the same numbers, verbatim */
 int fit_when_k_message(const fit_eta_k* e, char* buf, int32_t buflen);
+
+/* ---- priority-order backfill of multi-node jobs -----------------------------
+ * fit_place_tl for jobs of nodes_k nodes, the committing half of fit_when_k: jobs 0 .. j-1 in
+ * index order, each judged against the timeline AS THE JOBS BEFORE IT LEFT IT.  Partition
+ * rejection is fit_place_tl's (FIT_REJECTED, nothing consumed).  Otherwise, with need =
+ * max(nodes_k, 1) and d = max(1, ceil(wall / slot_min)): the start is the smallest s with cnt(s) >=
+ * need, the nodes are the need smallest (score, node id) among the members free from it —
+ * fit_when_k's row and node list, field for field — and (cpu, mem, gpu) is subtracted on slots
+ * [start, start + d) of EACH of them: a gang reserves on need nodes or on none.  Without a start the
+ * job is FIT_UNPLACED and consumes nothing.  A queue with every nodes_k <= 1 gives fit_place_tl's
+ * nodes, starts and timeline; job 0's result is fit_when_k's answer on the timeline as loaded; the
+ * node table (fit_read_nodes) is untouched.
+ * Host pointers; nodes_k may be NULL (= all 1); stats may be NULL.  out_node has j * kmax entries:
+ * out_node[q * kmax + i], i < need, are a placed job's nodes in key order and every other entry is
+ * -1; a rejected job has out_node[q * kmax] = FIT_REJECTED and the rest -1; an unplaced job has all
+ * entries -1 (FIT_UNPLACED).  out_start[q]: the start slot, -1 when the job is not placed.  j == 0
+ * returns 0 whatever the pointers are and zeroes stats.
+ * FIT_E_INVAL: NULL ctx / arrays, j < 0, kmax < 1 or kmax > FIT_MAX_K, any max(nodes_k, 1) > kmax,
+ * any negative demand — the whole call fails and the timeline is unchanged (the batch is validated
+ * before the first reservation).  FIT_E_STATE: before fit_load_nodes; without a timeline loaded; on a
+ * context created with world > 1 or FIT_FLAG_COLLECTIVES.  A HIP error once reservations have begun
+ * drops the timeline, as a watchdog trip of fit_place_tl does: FIT_E_STATE until fit_load_timeline.
+ * stats: jobs, placed, unplaced, rejected, components, ms_total, ms_device (HIP events on the
+ * context's stream) and engine = 4; every other field is 0 (ms_arb_wait too: no lock is taken).
+ * Bounded launches, one workgroup per partition component, at most 16,384 jobs of a component per
+ * launch; no persistent grid: the call neither takes the per-GPU persistent-launch lock nor needs
+ * the watchdog.  One workgroup walks a component's nodes per job, so a table that is a single large
+ * component is slow. */
+int fit_place_tl_k(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                   int32_t* out_node /* j * kmax */, int32_t* out_start /* j */, fit_stats* stats);
+/* Same with device pointers (inputs resident in HBM, outputs written in HBM). */
+int fit_place_tl_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                          int32_t* out_node /* j * kmax */, int32_t* out_start /* j */, fit_stats* stats);
 
 /* ---- how many more copies of a job fit now ---------------------------------
  * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a

@@ -323,6 +323,9 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> wk_node, wk_diff;
     HBuf<int32_t> h_wk_node;
     DBuf<unsigned long long> wk_top;
+    // fit_place_tl_k: the placed count of the commit launches (device, pinned)
+    DBuf<int32_t> ptlk_cnt;
+    HBuf<int32_t> h_ptlk;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1466,6 +1469,79 @@ int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_place_tl_k
+// classify the batch, the jobs of each component in index order
+// (launch_joblists), ONE synchronisation that brings back the bad-input flag, the reject count and
+// the component offsets — so a bad batch fails before anything is reserved — then k_ptlk_commit per
+// chunk of PTLK_CHUNK jobs of every component's list, one workgroup per component.  Bounded
+// launches on the context's stream, nothing waits on another workgroup: no launch lock, no
+// watchdog.  Device pointers; out (J * kmax) and outs (J) are valid on return.
+int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32_t* out, int32_t* outs,
+                    fit_stats* stats) {
+    const double t0 = now_ms();
+    fit_stats S;
+    memset(&S, 0, sizeof S);
+    S.jobs = J;
+    S.engine = 4;
+    const int C = c->ncomp, H = c->tl_slots;
+    S.components = C;
+    hipStream_t st = c->st;
+    const size_t ns = 2 * ((size_t)C + 1) + 2;
+    if (c->jcomp.ensure(J) || c->jl.ensure(J) || c->jpk.ensure((size_t)J + 1) ||
+        c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + ns) || c->h_jls.ensure(ns) ||
+        c->ptlk_cnt.ensure(1) || c->h_ptlk.ensure(1))
+        return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], st));
+    HIP_TRY(launch_ptlk_classify(st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, J, out, outs,
+                                 c->jcomp.p));
+    int32_t* g = c->jls.p + joblists_scratch_ints(J);  // [0] rejected, [1] bad input, then jb and mb
+    int32_t* jbd = g + 2;
+    HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
+    HIP_TRY(hipEventRecord(c->ev[1], st));
+    HIP_TRY(hipMemcpyAsync(c->h_jls.p, g, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->h_jls.p[1]) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > kmax");
+    S.rejected = c->h_jls.p[0];
+    int32_t maxlen = 0;  // the longest component job list
+    for (int k = 0; k < C; ++k) maxlen = std::max(maxlen, c->h_jls.p[2 + k + 1] - c->h_jls.p[2 + k]);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    S.ms_device = ms;
+    if (maxlen > 0) {
+        int32_t chunk = PTLK_CHUNK;  // FIT_PTLK_CHUNK: tests put the launch seam inside a small batch
+        if (const char* e = getenv("FIT_PTLK_CHUNK")) chunk = std::max(1, std::min(atoi(e), PTLK_CHUNK));
+        const int threads = ptlk_threads(c->cls_maxn);
+        ExplainComps ec;
+        ec.ncomp = C;
+        for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+        HIP_TRY(hipMemsetAsync(c->ptlk_cnt.p, 0, sizeof(int32_t), st));
+        HIP_TRY(hipEventRecord(c->ev[3], st));
+        // from the first commit launch on the run lists may be partly reserved: an error drops the
+        // timeline, as a watchdog trip of fit_place_tl does
+        hipError_t e = hipSuccess;
+        int32_t done = 0;
+        for (; done < maxlen && e == hipSuccess; done += chunk)
+            e = launch_ptlk_commit(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd, done, chunk,
+                                   d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs, c->ptlk_cnt.p);
+        if (e != hipSuccess && done <= chunk) return fail(FIT_E_HIP, "k_ptlk_commit launch failed: %s", hipGetErrorString(e));
+        if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(c->h_ptlk.p, c->ptlk_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+        if (e != hipSuccess) {
+            c->have_tl = false;
+            return fail(FIT_E_HIP, "fit_place_tl_k: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
+        }
+        S.ms_device += ms;
+        S.placed = c->h_ptlk.p[0];
+    }
+    S.unplaced = J - S.placed - S.rejected;
+    S.ms_total = now_ms() - t0;
+    if (stats) *stats = S;
+    return 0;
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -2110,6 +2186,51 @@ int fit_place_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));
     return 0;
+}
+
+// fit_place_tl_k / fit_place_tl_k_device: fit_when_k's tests (a query name: a sharded context is
+// refused); nodes_k against kmax and the demands are the device's flag word
+static int check_place_tl_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_place_tl_k", 1);
+    if (rc) return rc;
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+int fit_place_tl_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax, int32_t* out_node,
+                   int32_t* out_start, fit_stats* stats) {
+    int rc = check_place_tl_k_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    JobCols d;
+    rc = stage_columns(c, j, cpu, mem, gpu, wall, part, true, nk, d);
+    if (rc) return rc;
+    const size_t nn = (size_t)j * kmax;
+    if (c->out.ensure(nn) || c->outs.ensure(j)) return FIT_E_OOM;
+    rc = place_tl_k_impl(c, j, d, kmax, c->out.p, c->outs.p, stats);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_node, c->out.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(out_start, c->outs.p, sizeof(int32_t) * j, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+int fit_place_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
+                          int32_t* out_node, int32_t* out_start, fit_stats* stats) {
+    const int rc = check_place_tl_k_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return place_tl_k_impl(c, j, {cpu, mem, gpu, wall, part, nk}, kmax, out_node, out_start, stats);
 }
 
 int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {

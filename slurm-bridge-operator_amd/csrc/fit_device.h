@@ -220,6 +220,23 @@ hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab,
                               int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
                               int32_t* diff, unsigned long long* top, void* out, int32_t* out_node);
 
+// ---- fit_place_tl_k (fit_place_tl_k.hip) -------------------------------
+// One workgroup per component walks its jobs in order; a launch takes at most PTLK_CHUNK jobs of
+// every component's list, so a launch is bounded whatever J is.
+constexpr int PTLK_CHUNK = 16384;   // jobs of a component per k_ptlk_commit launch
+constexpr int PTLK_THREADS = 1024;  // threads of a commit workgroup, at most
+hipError_t launch_ptlk_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t nj,
+                                int32_t* out_node, int32_t* out_start, int8_t* jcomp);
+int ptlk_threads(int32_t max_component_nodes);
+size_t ptlk_lds_bytes(int threads, int32_t H);
+hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
+                              const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                              const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
+                              int32_t* out_start, int32_t* placed);
+
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
 enum RoomCode : int32_t {

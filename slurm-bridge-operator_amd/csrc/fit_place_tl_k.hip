@@ -1,0 +1,339 @@
+// fit_place_tl_k.hip — priority-order backfill of multi-node jobs on the timeline: per job, in
+// index order, fit_when_k's common start and node list against the run lists as the jobs before it
+// left them, then the reservation on every one of its nodes (include/fitgpu.h fit_place_tl_k;
+// DESIGN.md §2g, §3.15).  gfx950.
+//
+// Ordinary bounded launches on the context's stream:
+//   k_ptlk_classify : per job, the partition-limit rule (k_whenk_classify's), the reject result in
+//                     out_node / out_start, and the job's component in launch_joblists' coding
+//                     (-2 rejected, -3 bad input, -1 no member node)
+//   launch_joblists : the jobs of each component, in index order inside a component
+//   k_ptlk_commit   : ONE workgroup per partition component, looping over its component's jobs of
+//                     the chunk in order.  Per job: (count) threads stride over the component's
+//                     nodes, walk each whole run list and add +1 / -1 at the ends of every stretch
+//                     of feasible starts to a difference array in LDS; (pick) one wave takes the
+//                     prefix sum, 64 slots per step, and leaves at the first s with cnt >= need;
+//                     (nodes) the count walk also scores each node's FIRST window, and a thread
+//                     keeps its 8 smallest keys sorted in registers: when no node is free before
+//                     the start these are the answer; otherwise threads evaluate the one window
+//                     [start, start + d) on their nodes again.  `need` rounds of an LDS 64-bit
+//                     minimum take the workgroup's smallest; (reserve) one wave per pick reserves
+//                     with tl_reserve_any and refreshes the node's header.
+// A component's rows are read and written by its workgroup alone, so nothing here waits for another
+// workgroup: no persistent grid, no launch lock, no watchdog.  Between jobs the waves of the
+// workgroup hand the run lists on through __syncthreads(), i.e. a workgroup-scope release before and
+// acquire after the barrier: all waves share the CU's vector L1, which the CU's own stores keep
+// current.  The kernel end orders one launch against the next.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "fit_device.h"
+#include "fit_tl_reserve.h"
+#include "fit_tl_walk.h"
+
+namespace fitgpu {
+
+constexpr int PTLK_RWAVES = FIT_KMAX;  // waves that reserve side by side, one pick each
+static_assert(TL_HEAD % 4 == 0 && TL_MAX_SLOTS % 4 == 0, "the walks load four Seg at a time inside a slab row");
+static_assert(PTLK_THREADS % 64 == 0 && PTLK_THREADS <= 1024, "whole waves, one workgroup");
+
+__global__ __launch_bounds__(256) void k_ptlk_classify(
+    const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
+    const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk,
+    int32_t kmax, int32_t nj, const int32_t* __restrict__ ptab /* [4][32]: time, cpus, mem, comp */, int32_t np,
+    int32_t* __restrict__ out_node, int32_t* __restrict__ out_start, int8_t* __restrict__ jcomp) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nj) return;
+    const int p = jpart[q];
+    const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
+    const int32_t need = max(jk ? (int32_t)jk[q] : 1, 1);
+    bool rej = p >= np;
+    if (!rej) {
+        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
+        rej = (mt >= 0 && w > mt) || (mc >= 0 && c > mc) || (mm >= 0 && m > mm);
+    }
+    int comp = rej ? -2 : ptab[96 + p];  // -1: no node carries the partition's bit (unplaced)
+    if (c < 0 || m < 0 || g < 0 || w < 0 || need > kmax) comp = -3;  // the whole call fails (FIT_E_INVAL)
+    for (int i = 0; i < kmax; ++i) out_node[(int64_t)q * kmax + i] = rej && i == 0 ? -2 : -1;
+    out_start[q] = -1;
+    jcomp[q] = (int8_t)comp;
+}
+
+// LDS of k_ptlk_commit, all in the dynamic region and every part a multiple of 16 bytes: the
+// reservation scratch of H + 2 Seg per reserving wave, the picks, the start and the difference array.
+__host__ __device__ inline int ptlk_rwaves(int threads) {
+    return threads / 64 < PTLK_RWAVES ? threads / 64 : PTLK_RWAVES;
+}
+__host__ __device__ inline size_t ptlk_scr_bytes(int threads, int32_t H) {
+    return sizeof(Seg) * (size_t)ptlk_rwaves(threads) * (H + 2);
+}
+
+// grid = components; jl: the component-ordered job list, jb[c] .. jb[c + 1] component c's range of
+// it; this launch takes positions [t0, t0 + chunk) of every component's range.
+__global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
+    TlHdr* hdr, Seg* slab, ExplainComps C, int32_t H, int32_t slot_min, const int32_t* __restrict__ jl,
+    const int32_t* __restrict__ jb, int32_t t0, int32_t chunk, const int32_t* __restrict__ jcpu,
+    const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu, const int32_t* __restrict__ jwall,
+    const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk, int32_t kmax, int32_t* out_node,
+    int32_t* out_start, int32_t* __restrict__ placed_total) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int c = blockIdx.x;
+    if (c >= C.ncomp) return;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int rw = ptlk_rwaves(nt);
+    Seg* scr = reinterpret_cast<Seg*>(smem);
+    unsigned long long* pick = reinterpret_cast<unsigned long long*>(smem + ptlk_scr_bytes(nt, H));
+    int32_t* sh = reinterpret_cast<int32_t*>(pick + FIT_KMAX);  // sh[0]: the job's start
+    int32_t* diff = sh + 4;                                     // H + 1 words
+    const int nb = C.nb[c], ne = C.nb[c + 1];
+    const int lo = min(jb[c + 1], jb[c] + t0), hi = min(jb[c + 1], lo + chunk);
+    int32_t placed = 0;
+    for (int i = tid; i <= H; i += nt) diff[i] = 0;
+    __syncthreads();
+    for (int t = lo; t < hi; ++t) {  // every branch on a job's values below is workgroup-uniform
+        const int q = jl[t];
+        const int32_t cpu = jcpu[q], mem = jmem[q], gpu = jgpu[q];
+        const int32_t need = min(max(jk ? (int32_t)jk[q] : 1, 1), min(kmax, FIT_KMAX));
+        const int64_t dw = ((int64_t)max(jwall[q], 0) + slot_min - 1) / slot_min;
+        const int32_t d = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));  // k_whenk_classify's `dur`
+        const uint32_t pbit = 1u << (jpart[q] & 31);
+        if (d > H) continue;  // no window inside the horizon: unplaced, nothing touched
+        // the last job's readers of pick[] are behind its closing barrier; two barriers lie between
+        // this reset and the first minimum
+        if (tid < FIT_KMAX) pick[tid] = KEY_INF;
+
+        // ---- count: +1 at a, -1 at b - d + 1 for every feasible stretch [a, b) of at least d slots.
+        // On the way a thread keeps, sorted, the 8 smallest §2b keys of its nodes: the node's earliest
+        // start e_n, then the score of the window [e_n, e_n + d), then the position (tl_step's rule)
+        uint64_t key[FIT_KMAX];
+#pragma unroll
+        for (int i = 0; i < FIT_KMAX; ++i) key[i] = KEY_INF;
+        for (int x = nb + tid; x < ne; x += nt) {
+            const TlHdr h = hdr[x];
+            // the header's column ceilings reject a node without a walk (when_node's rule)
+            if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
+            const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
+            const int cn = min(h.cnt, TL_MAX_SLOTS);
+            int32_t s0 = 0, ra = -1;  // start of the current run, of the current feasible stretch (-1: none)
+            int32_t mc = 0, mm = 0, mg = 0;         // minima of the current stretch's runs so far
+            int32_t ks = -1, kc = 0, km = 0, kg = 0;  // the first window: its start and minima, frozen
+            auto step = [&](bool vr, int32_t rc, int32_t rm, int32_t rg, int32_t e) {
+                const bool f = vr & (rc >= cpu) & (rm >= mem) & (rg >= gpu);
+                if (!f && ra >= 0) {
+                    if (s0 - ra >= d) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
+                        atomicAdd(&diff[ra], 1);
+                        atomicAdd(&diff[s0 - d + 1], -1);
+                    }
+                    ra = -1;
+                }
+                const int32_t e1 = min(max(e, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
+                if (f && s0 < H) {
+                    const bool nw = ra < 0;
+                    ra = nw ? s0 : ra;
+                    mc = nw ? rc : min(mc, rc);
+                    mm = nw ? rm : min(mm, rm);
+                    mg = nw ? rg : min(mg, rg);
+                    if (ks < 0 && e1 - ra >= d) {  // the run that holds slot ra + d - 1 closes the first window
+                        ks = ra;
+                        kc = mc;
+                        km = mm;
+                        kg = mg;
+                    }
+                }
+                s0 = e1;
+            };
+#pragma unroll
+            for (int i = 0; i < TL_HEAD; ++i)
+                if (i < cn) step(true, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, h.head[i].end);
+            for (int i = TL_HEAD; i < cn; i += 4) {  // four Seg per wait, as when_node
+                Seg r4[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (i + k < cn) step(true, r4[k].cpu, r4[k].mem, r4[k].gpu, r4[k].end);
+            }
+            step(false, 0, 0, 0, H);
+            if (ks < 0) continue;
+            uint64_t k = tl_key(ks, kc, km, kg, cpu, mem, gpu, (uint32_t)x);
+#pragma unroll
+            for (int i = 0; i < FIT_KMAX; ++i) {  // sorted insert: k carries the larger one on
+                const uint64_t lo2 = min(k, key[i]);
+                k = max(k, key[i]);
+                key[i] = lo2;
+            }
+        }
+        __syncthreads();
+
+        // ---- pick: cnt(s) is the prefix sum of the differences; starts lie in [0, H - d]
+        if (wave == 0) {
+            int32_t carry = 0, first = -1, early = 0;
+            for (int base = 0; base < H; base += 64) {
+                const int s = base + lane;
+                int32_t v = s < H ? diff[s] : 0;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int32_t u = __shfl_up(v, off);
+                    if (lane >= off) v += u;
+                }
+                v += carry;  // cnt(s)
+                const uint64_t hit = __ballot(s < H && v >= need);
+                const uint64_t some = __ballot(s < H && v > 0);
+                if (hit) {
+                    first = base + __builtin_ctzll(hit);
+                    early |= (some & ((1ull << __builtin_ctzll(hit)) - 1ull)) != 0;
+                    break;
+                }
+                early |= some != 0;
+                carry = __shfl(v, 63);
+            }
+            if (lane == 0) {
+                sh[0] = first;
+                sh[1] = early;  // some node is free before the start: its first window is not the job's
+            }
+        }
+        __syncthreads();
+        const int32_t start = sh[0];
+        // the array is read; the next count adds to it behind at least one more barrier
+        for (int i = tid; i <= H; i += nt) diff[i] = 0;
+        if (start < 0) {  // fewer than `need` nodes free together anywhere: unplaced
+            __syncthreads();
+            continue;
+        }
+
+        // ---- nodes: when no node is free before the start, the members free from it are exactly those
+        // whose earliest start it is, and their windows are the ones the count walk scored: the keys are
+        // there, in (score, position) order behind the common start.  Otherwise the one window
+        // [start, start + d) gives feasibility and the minima (k_whenk_nodes).
+        const int32_t stop = start + d;  // <= H: the differences only mark starts s with s + d <= H
+        if (sh[1]) {
+#pragma unroll
+            for (int i = 0; i < FIT_KMAX; ++i) key[i] = KEY_INF;
+            for (int x = nb + tid; x < ne; x += nt) {
+                const TlHdr h = hdr[x];
+                if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
+                const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
+                const int cn = min(h.cnt, TL_MAX_SLOTS);
+                int32_t mc = 0x7fffffff, mm = 0x7fffffff, mg = 0x7fffffff;
+                bool ok = true, closed = false;  // closed: the runs seen cover the window
+                // runs end in increasing order and the walk stops at the first that reaches `stop`, so a run
+                // meets the window exactly when it ends behind `start`
+                auto run = [&](const Seg& r) {
+                    if (r.end <= start) return;
+                    ok = (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
+                    mc = min(mc, r.cpu);
+                    mm = min(mm, r.mem);
+                    mg = min(mg, r.gpu);
+                    closed = r.end >= stop;
+                };
+#pragma unroll
+                for (int i = 0; i < TL_HEAD; ++i)
+                    if (i < cn && ok && !closed) run(h.head[i]);
+                for (int i = TL_HEAD; i < cn && ok && !closed; i += 4) {
+                    Seg r4[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (i + k < cn && ok && !closed) run(r4[k]);
+                }
+                if (!ok || !closed) continue;
+                uint64_t k = tl_key(start, mc, mm, mg, cpu, mem, gpu, (uint32_t)x);
+#pragma unroll
+                for (int i = 0; i < FIT_KMAX; ++i) {  // sorted insert: k carries the larger one on
+                    const uint64_t lo2 = min(k, key[i]);
+                    k = max(k, key[i]);
+                    key[i] = lo2;
+                }
+            }
+        }
+        // either way a key that counts carries `start` in its top bits; a later first window does not
+        // (KEY_INF is no node's key: check_timeline_args keeps the positions one short of the field)
+        auto counts = [&](uint64_t k) { return k != KEY_INF && (int32_t)(k >> 54) == start; };
+        // the workgroup's `need` smallest, one slot of pick[] per round: keys are distinct (the
+        // position), so exactly one thread owns a round's minimum and moves its list up
+        int got = 0;
+        for (int r = 0; r < need; ++r) {
+            if (counts(key[0])) atomicMin(&pick[r], (unsigned long long)key[0]);
+            __syncthreads();
+            const uint64_t w = pick[r];
+            if (w == KEY_INF) break;
+            if (key[0] == w) {
+#pragma unroll
+                for (int i = 0; i + 1 < FIT_KMAX; ++i) key[i] = key[i + 1];
+                key[FIT_KMAX - 1] = KEY_INF;
+            }
+            ++got;
+        }
+        if (got < need) {  // cannot happen: cnt(start) >= need nodes passed the same test.  All or nothing.
+            __syncthreads();
+            continue;
+        }
+
+        // ---- reserve: one wave per pick, each with its own scratch; the node's header follows its list
+        if (wave < rw)
+            for (int r = wave; r < need; r += rw) {
+                const uint32_t pos = (uint32_t)pick[r] & TL_POS_MASK;  // in [nb, ne): a position this workgroup read
+                TlHdr* hp = hdr + pos;
+                Seg* sg = slab + (int64_t)pos * TL_MAX_SLOTS;
+                const int n = min(hp->cnt, TL_MAX_SLOTS);
+                const int nn = tl_reserve_any(sg, n, start, stop, cpu, mem, gpu, scr + (size_t)wave * (H + 2));
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the list's writes before its re-read
+                if (lane < TL_HEAD) hp->head[lane] = lane < nn ? sg[lane] : Seg{H, -1, -1, -1};
+                if (lane == 0) {
+                    hp->cnt = nn;
+                    out_node[(int64_t)q * kmax + r] = hp->orig;
+                }
+            }
+        if (tid == 0) {
+            out_start[q] = start;
+            ++placed;
+        }
+        __syncthreads();  // the next job reads what these waves stored
+    }
+    if (tid == 0 && placed) atomicAdd(placed_total, placed);
+}
+
+// Classify the whole batch: out_node (nj * kmax words) and out_start (nj) hold the reject results
+// and -1 elsewhere afterwards, jcomp the components for launch_joblists.
+hipError_t launch_ptlk_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
+                                const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t nj,
+                                int32_t* out_node, int32_t* out_start, int8_t* jcomp) {
+    if (nj <= 0) return hipSuccess;
+    if (kmax < 1 || kmax > FIT_KMAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ptlk_classify, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jpart, jk,
+                       kmax, nj, ptab, np, out_node, out_start, jcomp);
+    return hipGetLastError();
+}
+
+// threads of a commit workgroup: a thread per node of the largest component, whole waves, at most
+// PTLK_THREADS
+int ptlk_threads(int32_t max_component_nodes) {
+    return std::max(64, std::min(PTLK_THREADS, (max_component_nodes + 63) / 64 * 64));
+}
+
+size_t ptlk_lds_bytes(int threads, int32_t H) {
+    return ptlk_scr_bytes(threads, H) + sizeof(unsigned long long) * FIT_KMAX + sizeof(int32_t) * 4 +
+           sizeof(int32_t) * (((size_t)H + 1 + 3) & ~(size_t)3);
+}
+
+// Positions [t0, t0 + chunk) of every component's job list, in order, on stream st.
+hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
+                              const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                              const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
+                              int32_t* out_start, int32_t* placed) {
+    if (C.ncomp < 1 || C.ncomp > 32 || threads < 64 || threads > PTLK_THREADS || threads % 64 || H < 1 ||
+        H > TL_MAX_SLOTS || slot_min < 1 || kmax < 1 || kmax > FIT_KMAX || t0 < 0 || chunk < 1 || chunk > PTLK_CHUNK)
+        return hipErrorInvalidValue;
+    const size_t lds = ptlk_lds_bytes(threads, H);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ptlk_commit, dim3(C.ncomp), dim3(threads), lds, st, hdr, slab, C, H, slot_min, jl, jb, t0,
+                       chunk, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, out_node, out_start, placed);
+    return hipGetLastError();
+}
+
+}  // namespace fitgpu

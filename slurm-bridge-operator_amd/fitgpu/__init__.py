@@ -656,6 +656,34 @@ class Engine:
         check(lib().fit_when_k_ms(self._h, C.byref(ms)), "fit_when_k_ms")
         return ms.value
 
+    # ---- priority-order backfill of multi-node jobs ------------------------
+    def place_tl_k(self, jobs, kmax: int | None = None):
+        """The queue in index order, each job of jobs.nodes_k nodes reserved on the timeline as the
+        jobs before it left it (fit_place_tl_k): (nodes[J, kmax], start[J], stats).  A placed job's
+        nodes in key order, -1 elsewhere; nodes[q, 0] = FIT_REJECTED for a rejected job; start -1
+        when not placed.  kmax None: the largest nodes_k of the batch (at least 1)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        j = len(part)
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j else 1
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        start = np.full(j, -1, np.int32)
+        st = FitStats()
+        check(lib().fit_place_tl_k(self._h, j, *[_ptr(c) for c in cols], _ptr(part), _ptr(k), int(kmax), _ptr(nodes),
+                                   _ptr(start), C.byref(st)), "fit_place_tl_k")
+        return nodes, start, st.as_dict()
+
+    def place_tl_k_device(self, cpu, mem, gpu, wall, part, nodes_k, out_node, out_start, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1); writes
+        out_node (J * kmax int32) and out_start (J int32).  Returns the stats."""
+        st = FitStats()
+        check(lib().fit_place_tl_k_device(self._h, int(cpu.numel()), _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
+                                          _ptr(part), _ptr(nodes_k) if nodes_k is not None else None, int(kmax),
+                                          _ptr(out_node), _ptr(out_start), C.byref(st)), "fit_place_tl_k_device")
+        return st.as_dict()
+
     # ---- how many more copies of a job fit now (DESIGN.md §2e) ---------------------------
     def room(self, jobs):
         """Every job judged alone against the current node table (fit_room): a structured array of

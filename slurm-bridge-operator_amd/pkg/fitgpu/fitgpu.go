@@ -342,6 +342,37 @@ func (e *Engine) PlaceBackfill(j Jobs) (node, start []int32, st Stats, err error
 	return node, start, st, check(rc)
 }
 
+// PlaceTLK is PlaceBackfill for jobs of NodesK nodes (DESIGN.md §2g): the queue in index order, each
+// job reserved on all of its nodes from one common start, against the timeline as the jobs before it
+// left it.  nodes has kmax entries per job: a placed job's nodes in key order, -1 elsewhere;
+// nodes[q*kmax] is Rejected for partition limits, and Unplaced (like the rest) when no start has
+// NodesK nodes free together inside the horizon.  start[q] is the start slot, -1 when not placed.
+// NodesK may be empty (every job takes one node); otherwise it has one entry per job.
+func (e *Engine) PlaceTLK(j Jobs, kmax int) (nodes, start []int32, st Stats, err error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return nil, nil, st, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part)) ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, nil, st, errLen
+	}
+	nodes, start = make([]int32, cnt*kmax), make([]int32, cnt)
+	if cnt == 0 {
+		return nodes, start, st, nil
+	}
+	var nk *C.uint16_t // NULL: every job takes one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	rc := C.fit_place_tl_k(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])),
+		nk, C.int32_t(kmax), (*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&start[0])), &st)
+	runtime.KeepAlive(e)
+	return nodes, start, st, check(rc)
+}
+
 // Eta codes (fit_eta.code, include/fitgpu.h): when a job can start.  EtaPartition .. EtaNoNodes
 // are WhyPartition .. WhyNoNodes.
 const (
