@@ -432,6 +432,45 @@ int fit_place_tl_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int
                           const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
                           int32_t* out_node /* j * kmax */, int32_t* out_start /* j */, fit_stats* stats);
 
+/* ---- hand reservations back to the timeline ---------------------------------
+ * The inverse of fit_place_tl / fit_place_tl_k, for a deleted pod or a running job that ends
+ * before its end_time: demand windows are ADDED to the current timeline (what fit_read_timeline
+ * returns).  Row q is one job in the columns a caller gave to, and got from, fit_place_tl_k:
+ * per-node demand (cpu, mem, gpu)[q], wall[q], nodes_k[q], node[q * kmax + i] and start[q]; with
+ * kmax = 1 and nodes_k = NULL they are fit_place_tl's.  A row with start[q] < 0 is skipped whatever
+ * else it holds, so a placement's outputs go back verbatim, unplaced and rejected rows included.
+ * A live row, with need = max(nodes_k, 1) and d = max(1, ceil(wall / slot_min)), covers slots
+ * [start, min(start + d, H)) of each of node[q * kmax .. + need); entries i >= need are ignored.
+ * Per slot and column a value of -1 stays -1 (unusable slot, node in no partition, column loaded
+ * negative: nothing was ever reserved there) and any other value v becomes min(v + demand,
+ * INT32_MAX).  Both rules commute and associate: the result does not depend on the order of the
+ * rows, and two calls give what one gives.  Run lists stay canonical and the node headers follow.
+ * Unplacing every placed row of a placement restores the timeline it started from, bit for bit;
+ * start = 0, wall = rem_min on a running job's nodes removes it from the loaded timeline (as long
+ * as no value was clamped).  The node table (fit_read_nodes) is untouched.
+ * Host pointers; nodes_k may be NULL (= all 1); *applied (may be NULL) is the number of (row, node)
+ * windows added: the sum of need over the live rows.  j == 0 returns 0 whatever the pointers are.
+ * FIT_E_INVAL: NULL ctx / arrays, j < 0, kmax < 1 or kmax > FIT_MAX_K; in a live row a negative
+ * demand, need > kmax, start >= H, a node id outside [0, n) or the same node twice — the whole call
+ * fails and the timeline is unchanged (the batch is validated before the first write).
+ * FIT_E_STATE: before fit_load_nodes; without a timeline loaded; on a context created with world > 1
+ * or FIT_FLAG_COLLECTIVES.  A HIP error once writing has begun drops the timeline, as in
+ * fit_place_tl_k: FIT_E_STATE until fit_load_timeline.
+ * Bounded launches, one wave per touched node, at most 16,384 rows per launch sequence; no
+ * persistent grid: the call neither takes the per-GPU persistent-launch lock nor needs the
+ * watchdog. */
+int fit_unplace_tl(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* nodes_k /* NULL = all 1 */, int32_t kmax,
+                   const int32_t* node /* j * kmax */, const int32_t* start /* j */,
+                   int64_t* applied /* may be NULL: (row, node) windows added */);
+/* Same with device pointers (inputs resident in HBM); applied is a host pointer. */
+int fit_unplace_tl_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* nodes_k, int32_t kmax, const int32_t* node,
+                          const int32_t* start, int64_t* applied);
+/* Device time (HIP events) of the last successful fit_unplace_tl / fit_unplace_tl_device, as
+ * fit_when_k_ms; FIT_E_STATE before the first. */
+int fit_unplace_tl_ms(fit_ctx* ctx, double* ms);
+
 /* ---- how many more copies of a job fit now ---------------------------------
  * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a
  * partition takes of one shape, the resource that runs out first: fit_room judges each of J jobs

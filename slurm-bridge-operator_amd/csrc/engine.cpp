@@ -326,6 +326,14 @@ struct fit_ctx : CtxHandles {
     // fit_place_tl_k: the placed count of the commit launches (device, pinned)
     DBuf<int32_t> ptlk_cnt;
     HBuf<int32_t> h_ptlk;
+    // fit_unplace_tl: the staged node lists and starts of the host entry point, node id -> position,
+    // per-position window count / range start / scatter cursor, the touched positions and the
+    // windows of one chunk, the counters (touched, handed out, bad flag, pad, windows per chunk) with
+    // their pinned copy, and the *_ms diagnostic
+    DBuf<int32_t> utl_node, utl_start, utl_inv, utl_cnt, utl_first, utl_fill, utl_touched, utl_g;
+    DBuf<UtlWin> utl_win;
+    HBuf<int32_t> h_utl;
+    double utl_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1542,6 +1550,68 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_unplace_tl
+// node id -> position, the check of the WHOLE batch, ONE synchronisation
+// that brings back the bad-input flag and the window count of every chunk — so a bad batch fails
+// before anything is written — then count, offsets, scatter and apply per chunk of UTL_CHUNK rows.
+// Bounded launches on the context's stream, nothing waits on another workgroup: no launch lock, no
+// watchdog.  Device pointers; *applied (host, may be null) is valid on return.
+int unplace_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                    const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
+                    int64_t* applied) {
+    const int H = c->tl_slots;
+    hipStream_t st = c->st;
+    int32_t chunk = UTL_CHUNK;  // FIT_UTL_CHUNK: tests put the launch seam inside a small batch
+    if (const char* e = getenv("FIT_UTL_CHUNK")) chunk = std::max(1, std::min(atoi(e), UTL_CHUNK));
+    const int64_t nchunks = ((int64_t)J + chunk - 1) / chunk;
+    const size_t ng = 4 + (size_t)nchunks, np = std::max(c->nn, 1);
+    const size_t wcap = (size_t)std::min(J, chunk) * kmax;
+    if (c->utl_inv.ensure(std::max(c->n, 1)) || c->utl_cnt.ensure(np) || c->utl_first.ensure(np) ||
+        c->utl_fill.ensure(np) || c->utl_touched.ensure(std::min(wcap, np)) || c->utl_win.ensure(wcap) ||
+        c->utl_g.ensure(ng) || c->h_utl.ensure(ng))
+        return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], st));
+    HIP_TRY(hipMemsetAsync(c->utl_g.p, 0, sizeof(int32_t) * ng, st));
+    HIP_TRY(hipMemsetAsync(c->utl_cnt.p, 0, sizeof(int32_t) * np, st));
+    HIP_TRY(launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->utl_inv.p));
+    HIP_TRY(launch_utl_check(st, cpu, mem, gpu, nk, kmax, node, start, J, c->n, H, chunk, c->utl_g.p));
+    HIP_TRY(hipEventRecord(c->ev[1], st));
+    HIP_TRY(hipMemcpyAsync(c->h_utl.p, c->utl_g.p, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->h_utl.p[2])
+        return fail(FIT_E_INVAL, "a live row has a negative demand, nodes_k > kmax, start >= %d slots, a node id "
+                                 "outside [0, %d) or the same node twice", H, c->n);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    double dev_ms = ms;
+    int64_t total = 0;
+    for (int64_t k = 0; k < nchunks; ++k) total += c->h_utl.p[4 + k];
+    if (total > 0 && c->nn > 0) {
+        HIP_TRY(hipEventRecord(c->ev[3], st));
+        // from the first apply launch on the run lists may be partly written: an error drops the
+        // timeline, as in fit_place_tl_k
+        hipError_t e = hipSuccess;
+        for (int64_t k = 0; k < nchunks && e == hipSuccess; ++k) {
+            const int32_t t0 = (int32_t)(k * chunk);
+            e = launch_utl_chunk(st, c->tlhdr.p, c->slab.p, c->nn, H, c->tl_slot_min, cpu, mem, gpu, wall, nk, kmax,
+                                 node, start, t0, std::min<int32_t>(J - t0, chunk), c->h_utl.p[4 + k], c->n,
+                                 c->utl_inv.p, c->utl_cnt.p, c->utl_first.p, c->utl_fill.p, c->utl_touched.p,
+                                 c->utl_win.p, c->utl_g.p);
+        }
+        if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+        if (e != hipSuccess) {
+            c->have_tl = false;
+            return fail(FIT_E_HIP, "fit_unplace_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
+        }
+        dev_ms += ms;
+    }
+    c->utl_ms = dev_ms;
+    if (applied) *applied = total;
+    return 0;
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -2231,6 +2301,61 @@ int fit_place_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32
     }
     HIP_TRY(hipSetDevice(c->device));
     return place_tl_k_impl(c, j, {cpu, mem, gpu, wall, part, nk}, kmax, out_node, out_start, stats);
+}
+
+// fit_unplace_tl / fit_unplace_tl_device: fit_place_tl_k's tests (a query name: a sharded context
+// is refused); the rows themselves are the device's flag word
+static int check_unplace_tl_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_unplace_tl", 1);
+    if (rc) return rc;
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+int fit_unplace_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
+                   int64_t* applied) {
+    int rc = check_unplace_tl_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (applied) *applied = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t m = j, nn = (size_t)j * kmax;
+    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) || (nk && c->jk.ensure(m)) ||
+        c->utl_node.ensure(nn) || c->utl_start.ensure(m))
+        return FIT_E_OOM;
+    const size_t b = sizeof(int32_t) * m;
+    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
+    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, sizeof(uint16_t) * m, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->utl_node.p, node, sizeof(int32_t) * nn, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->utl_start.p, start, b, hipMemcpyHostToDevice, c->st));
+    return unplace_tl_impl(c, j, c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, nk ? c->jk.p : nullptr, kmax,
+                           c->utl_node.p, c->utl_start.p, applied);
+}
+
+int fit_unplace_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node,
+                          const int32_t* start, int64_t* applied) {
+    const int rc = check_unplace_tl_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (applied) *applied = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return unplace_tl_impl(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, applied);
+}
+
+int fit_unplace_tl_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->utl_ms < 0) return fail(FIT_E_STATE, "no fit_unplace_tl yet");
+    *ms = c->utl_ms;
+    return 0;
 }
 
 int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {

@@ -125,9 +125,11 @@ struct alignas(16) Seg {
 constexpr int TL_HEAD = 4;  // runs of each node copied into its header (the scan's common case)
 
 // Per-node header of a run list, 96 B, contiguous over nodes (the scan streams it): run count,
-// the largest free value of each column over the timeline as built (reservations only lower
-// values, so it stays an upper bound: a job whose demand exceeds it can never fit the node),
-// partition mask, node id, and a copy of the first TL_HEAD runs.
+// a ceiling of each column — at least the largest free value on the node's timeline, so a job
+// whose demand exceeds it cannot fit the node now — partition mask, node id, and a copy of the
+// first TL_HEAD runs.  The ceilings are exact as built; reservations only lower values, which
+// leaves them upper bounds, and fit_unplace_tl, which raises values, raises them along
+// (k_utl_apply).
 struct alignas(32) TlHdr {
     int32_t cnt, cpu, mem, gpu;
     uint32_t mask;
@@ -236,6 +238,25 @@ hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab
                               const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                               const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
                               int32_t* out_start, int32_t* placed);
+
+// ---- fit_unplace_tl (fit_unplace_tl.hip) -------------------------------
+// Rows go in chunks of at most UTL_CHUNK per launch sequence (count, offsets, scatter, apply), so a
+// launch is bounded whatever J is.  One window of one node, as k_utl_scatter groups them by node:
+constexpr int UTL_CHUNK = 16384;  // rows per launch sequence
+struct alignas(16) UtlWin {
+    int32_t s, e;           // slots [s, e), clipped to the horizon
+    int32_t cpu, mem, gpu;  // the demand handed back
+    int32_t pad[3];
+};
+hipError_t launch_utl_inverse(hipStream_t st, const TlHdr* hdr, int32_t nn, int32_t n, int32_t* inv);
+hipError_t launch_utl_check(hipStream_t st, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                            const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t nj,
+                            int32_t n, int32_t H, int32_t chunk, int32_t* g);
+hipError_t launch_utl_chunk(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t H, int32_t slot_min,
+                            const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                            const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t t0,
+                            int32_t nj, int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
+                            int32_t* fill, int32_t* touched, UtlWin* win, int32_t* g);
 
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.

@@ -684,6 +684,43 @@ class Engine:
                                           _ptr(out_node), _ptr(out_start), C.byref(st)), "fit_place_tl_k_device")
         return st.as_dict()
 
+    # ---- hand reservations back to the timeline ----------------------------
+    def unplace_tl(self, jobs, node, start, kmax: int | None = None):
+        """Add the rows' demand windows back to the current timeline (fit_unplace_tl): jobs as given
+        to place_tl_k / place_tl, node[J, kmax] (or node[J] at kmax 1) and start[J] as they came
+        back; rows with start < 0 are skipped, so a placement's outputs go in verbatim.  kmax None:
+        node's second dimension (1 for a flat array).  Returns the (row, node) windows added."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        node = np.ascontiguousarray(node, np.int32)
+        start = np.ascontiguousarray(start, np.int32)
+        j = len(start)
+        if kmax is None:
+            kmax = node.shape[1] if node.ndim == 2 else 1
+        # a kmax outside 1..FIT_MAX_K is the library's error (FIT_E_INVAL), before it reads node
+        if any(len(c) != j for c in cols) or len(k) != j or (1 <= kmax <= FIT_MAX_K and node.size != j * kmax):
+            raise ValueError("jobs, node (J * kmax) and start (J) disagree on J")
+        applied = C.c_int64()
+        check(lib().fit_unplace_tl(self._h, j, *[_ptr(c) for c in cols], _ptr(k), int(kmax), _ptr(node), _ptr(start),
+                                   C.byref(applied)), "fit_unplace_tl")
+        return applied.value
+
+    def unplace_tl_device(self, cpu, mem, gpu, wall, nodes_k, node, start, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1; node has
+        J * kmax int32 entries).  Returns the (row, node) windows added."""
+        applied = C.c_int64()
+        check(lib().fit_unplace_tl_device(self._h, int(start.numel()), _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
+                                          _ptr(nodes_k) if nodes_k is not None else None, int(kmax), _ptr(node),
+                                          _ptr(start), C.byref(applied)), "fit_unplace_tl_device")
+        return applied.value
+
+    def unplace_tl_ms(self):
+        """Device time in ms of the last successful unplace_tl / unplace_tl_device (HIP events on the
+        context's stream, fit_unplace_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_unplace_tl_ms(self._h, C.byref(ms)), "fit_unplace_tl_ms")
+        return ms.value
+
     # ---- how many more copies of a job fit now (DESIGN.md §2e) ---------------------------
     def room(self, jobs):
         """Every job judged alone against the current node table (fit_room): a structured array of

@@ -373,6 +373,37 @@ func (e *Engine) PlaceTLK(j Jobs, kmax int) (nodes, start []int32, st Stats, err
 	return nodes, start, st, check(rc)
 }
 
+// UnplaceTL hands reservations back to the loaded timeline (DESIGN.md §2h): row q adds its per-node
+// demand to slots [start[q], start[q]+d) of node[q*kmax .. +max(NodesK,1)), d = max(1,
+// ceil(WallMin/slotMin)).  j, node and start are the columns given to, and returned by, PlaceTLK
+// (kmax 1: PlaceBackfill); rows with start[q] < 0 are skipped, so a placement's outputs go back
+// verbatim.  j.Part is not used.  A job seen to end early is unplaced with start 0 and its
+// remaining minutes as WallMin.  Returns the (row, node) windows added.
+func (e *Engine) UnplaceTL(j Jobs, kmax int, node, start []int32) (int64, error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return 0, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(start)) || len(node) != cnt*kmax ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return 0, errLen
+	}
+	if cnt == 0 {
+		return 0, nil
+	}
+	var nk *C.uint16_t // NULL: every job took one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	var applied C.int64_t
+	rc := C.fit_unplace_tl(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), nk, C.int32_t(kmax),
+		(*C.int32_t)(unsafe.Pointer(&node[0])), (*C.int32_t)(unsafe.Pointer(&start[0])), &applied)
+	runtime.KeepAlive(e)
+	return int64(applied), check(rc)
+}
+
 // Eta codes (fit_eta.code, include/fitgpu.h): when a job can start.  EtaPartition .. EtaNoNodes
 // are WhyPartition .. WhyNoNodes.
 const (
