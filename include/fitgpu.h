@@ -471,6 +471,48 @@ int fit_unplace_tl_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int
  * fit_when_k_ms; FIT_E_STATE before the first. */
 int fit_unplace_tl_ms(fit_ctx* ctx, double* ms);
 
+/* ---- move the timeline forward with the clock --------------------------------
+ * Slot 0 is "now" at the time of fit_load_timeline.  After a slots of slot_min minutes have passed,
+ * a running job's release slot ceil(rem_min / slot_min) and every reservation lie a slots earlier:
+ * the correct timeline is the old one moved left by a, plus a new slots at the far end.  With T the
+ * current dense timeline (what fit_read_timeline returns), H the loaded horizon and a' = min(a, H),
+ * per node n and per column:
+ *   T'[n][t] = T[n][t + a']                      for t < H - a';
+ *   for t >= H - a':  -1 if T[n][H - 1] == -1 in that column (a node past its avail_min, a column
+ *   loaded negative and a node in no partition stay unusable whatever the tail says, so a caller may
+ *   pass the same plain level for every node), otherwise tail_col[n], which must be >= -1 (-1 makes
+ *   the new slots unusable in that column).
+ * tail_cpu / tail_mem / tail_gpu: n entries each in the caller's node order — per node, its total
+ * minus the demand of the running jobs that end beyond the new horizon.  With all three NULL every
+ * column continues its slot H - 1 value; that is exact only when no reservation and no pending
+ * release reaches the old horizon edge (slot H - 1 then holds the node's plain level), and it does
+ * not commute with fit_unplace_tl of a window that touches slot H - 1.
+ * a == 0 returns 0 and changes nothing, whatever the pointers are.  The node table (fit_read_nodes),
+ * H, slot_min and the partitions are untouched.  Run lists stay canonical (the tail joins the last
+ * surviving run when all three columns agree; at most H - a' + 1 runs), cnt and head[] are
+ * refreshed and every header ceiling is recomputed exactly from the runs written — the only
+ * operation that lowers a ceiling on a timeline that lives for days.
+ * advance(a, tail) then advance(b, tail) equals advance(a + b, tail) for explicit tails; with
+ * explicit tails the call commutes with fit_unplace_tl: unplacing a window [s, e), e = min(s + d, H),
+ * before the advance equals unplacing [max(s - a', 0), e - a') after it, windows with e <= a' dropped
+ * (start' = max(start - a, 0), wall' = (e - a - start') * slot_min).
+ * FIT_E_INVAL: NULL ctx, a < 0, some but not all tail pointers NULL, a tail value < -1 — the whole
+ * call fails and the timeline is unchanged (the tails are validated before the first write).
+ * FIT_E_STATE: before fit_load_nodes; without a timeline loaded; on a context created with world > 1
+ * or FIT_FLAG_COLLECTIVES.  A HIP error once writing has begun drops the timeline, as in
+ * fit_place_tl_k: FIT_E_STATE until fit_load_timeline.
+ * Every node with a run list is touched, in place, one wave per list; bounded launches, no
+ * persistent grid: the call neither takes the
+ * per-GPU persistent-launch lock nor needs the watchdog. */
+int fit_advance_tl(fit_ctx* ctx, int32_t a, const int32_t* tail_cpu, const int32_t* tail_mem,
+                   const int32_t* tail_gpu /* host pointers, n entries, caller's node order; all NULL: continue */);
+/* Same with device pointers (tails resident in HBM). */
+int fit_advance_tl_device(fit_ctx* ctx, int32_t a, const int32_t* tail_cpu, const int32_t* tail_mem,
+                          const int32_t* tail_gpu);
+/* Device time (HIP events) of the last successful fit_advance_tl / fit_advance_tl_device with a > 0,
+ * as fit_unplace_tl_ms; FIT_E_STATE before the first. */
+int fit_advance_tl_ms(fit_ctx* ctx, double* ms);
+
 /* ---- how many more copies of a job fit now ---------------------------------
  * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a
  * partition takes of one shape, the resource that runs out first: fit_room judges each of J jobs

@@ -334,6 +334,11 @@ struct fit_ctx : CtxHandles {
     DBuf<UtlWin> utl_win;
     HBuf<int32_t> h_utl;
     double utl_ms = -1;
+    // fit_advance_tl: the staged tails of the host entry point, the bad-input flag with its pinned
+    // copy, and the *_ms diagnostic
+    DBuf<int32_t> atl_tc, atl_tm, atl_tg, atl_g;
+    HBuf<int32_t> h_atl;
+    double atl_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1612,6 +1617,42 @@ int unplace_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* me
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_advance_tl
+// with tails, their check and ONE synchronisation that brings the bad-input
+// flag back — so a bad tail fails before anything is written — then one launch, one wave per run
+// list.  Bounded launches on the context's stream, nothing waits on another workgroup:
+// no launch lock, no watchdog.  a >= 1; device pointers, n entries each, or all three null.
+int advance_tl_impl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
+    const int H = c->tl_slots;
+    hipStream_t st = c->st;
+    if (c->atl_g.ensure(1) || c->h_atl.ensure(1)) return FIT_E_OOM;
+    float ms = 0.f;
+    double dev_ms = 0;
+    if (tc && c->n > 0) {
+        HIP_TRY(hipEventRecord(c->ev[0], st));
+        HIP_TRY(hipMemsetAsync(c->atl_g.p, 0, sizeof(int32_t), st));
+        HIP_TRY(launch_atl_check(st, tc, tm, tg, c->n, c->atl_g.p));
+        HIP_TRY(hipEventRecord(c->ev[1], st));
+        HIP_TRY(hipMemcpyAsync(c->h_atl.p, c->atl_g.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->h_atl.p[0]) return fail(FIT_E_INVAL, "a tail value is below -1");
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        dev_ms = ms;
+    }
+    HIP_TRY(hipEventRecord(c->ev[3], st));
+    // from here on the run lists may be partly written: an error drops the timeline, as in fit_place_tl_k
+    hipError_t e = launch_atl_advance(st, c->tlhdr.p, c->slab.p, c->nn, c->n, H, std::min(a, H), tc, tm, tg);
+    if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+    if (e != hipSuccess) {
+        c->have_tl = false;
+        return fail(FIT_E_HIP, "fit_advance_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
+    }
+    c->atl_ms = dev_ms + ms;
+    return 0;
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -2355,6 +2396,42 @@ int fit_unplace_tl_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->utl_ms < 0) return fail(FIT_E_STATE, "no fit_unplace_tl yet");
     *ms = c->utl_ms;
+    return 0;
+}
+
+// fit_advance_tl / fit_advance_tl_device: the state tests of fit_unplace_tl, then a and the pointers
+static int check_advance_tl_args(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
+    const int rc = check_job_args(c, 0, {}, "fit_advance_tl", 1);
+    if (rc) return rc;
+    if (a < 0) return fail(FIT_E_INVAL, "a=%d", a);
+    if (a > 0 && ((!tc != !tm) || (!tc != !tg))) return fail(FIT_E_INVAL, "some but not all tail pointers are NULL");
+    return 0;
+}
+
+int fit_advance_tl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
+    const int rc = check_advance_tl_args(c, a, tc, tm, tg);
+    if (rc || a == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!tc || c->n == 0) return advance_tl_impl(c, a, nullptr, nullptr, nullptr);
+    const size_t m = c->n, b = sizeof(int32_t) * m;
+    if (c->atl_tc.ensure(m) || c->atl_tm.ensure(m) || c->atl_tg.ensure(m)) return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->atl_tc.p, tc, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->atl_tm.p, tm, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->atl_tg.p, tg, b, hipMemcpyHostToDevice, c->st));
+    return advance_tl_impl(c, a, c->atl_tc.p, c->atl_tm.p, c->atl_tg.p);
+}
+
+int fit_advance_tl_device(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
+    const int rc = check_advance_tl_args(c, a, tc, tm, tg);
+    if (rc || a == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return advance_tl_impl(c, a, tc, tm, tg);
+}
+
+int fit_advance_tl_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->atl_ms < 0) return fail(FIT_E_STATE, "no fit_advance_tl yet");
+    *ms = c->atl_ms;
     return 0;
 }
 

@@ -128,8 +128,8 @@ constexpr int TL_HEAD = 4;  // runs of each node copied into its header (the sca
 // a ceiling of each column — at least the largest free value on the node's timeline, so a job
 // whose demand exceeds it cannot fit the node now — partition mask, node id, and a copy of the
 // first TL_HEAD runs.  The ceilings are exact as built; reservations only lower values, which
-// leaves them upper bounds, and fit_unplace_tl, which raises values, raises them along
-// (k_utl_apply).
+// leaves them upper bounds, fit_unplace_tl, which raises values, raises them along (k_utl_apply,
+// DESIGN.md §2h), and fit_advance_tl recomputes them exactly (k_atl_move).
 struct alignas(32) TlHdr {
     int32_t cnt, cpu, mem, gpu;
     uint32_t mask;
@@ -257,6 +257,16 @@ hipError_t launch_utl_chunk(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, i
                             const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t t0,
                             int32_t nj, int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
                             int32_t* fill, int32_t* touched, UtlWin* win, int32_t* g);
+
+// ---- fit_advance_tl (fit_advance_tl.hip) -------------------------------
+// Every node position's run list moved left by a slots, 1 <= a <= H, in place: one wave per list.
+// *flag |= 1 when a tail entry of a caller's node id in [0, n) is below -1; nothing else is written
+hipError_t launch_atl_check(hipStream_t st, const int32_t* tc, const int32_t* tm, const int32_t* tg, int32_t n,
+                            int32_t* flag);
+// tc / tm / tg: n entries in the caller's node order (TlHdr::orig indexes them), or all three null:
+// every column continues its slot H - 1 value
+hipError_t launch_atl_advance(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t n, int32_t H, int32_t a,
+                              const int32_t* tc, const int32_t* tm, const int32_t* tg);
 
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.

@@ -721,6 +721,34 @@ class Engine:
         check(lib().fit_unplace_tl_ms(self._h, C.byref(ms)), "fit_unplace_tl_ms")
         return ms.value
 
+    # ---- move the timeline forward with the clock ---------------------------
+    def advance_tl(self, a: int, tail=None):
+        """Move the current timeline left by a slots (fit_advance_tl).  tail: int32 [n, 3] (cpu, mem,
+        gpu per node in the caller's order), the level of the a new slots at the far end wherever
+        slot H - 1 is not -1; None: every column continues its slot H - 1 value, which is exact only
+        when no reservation and no pending release reaches the old horizon edge."""
+        if tail is None:
+            check(lib().fit_advance_tl(self._h, int(a), None, None, None), "fit_advance_tl")
+            return
+        tail = np.asarray(tail, np.int32)
+        if tail.shape != (self.n, 3):
+            raise ValueError("tail must be [n, 3]")
+        cols = [np.ascontiguousarray(tail[:, i]) for i in range(3)]
+        check(lib().fit_advance_tl(self._h, int(a), *[_ptr(c) for c in cols]), "fit_advance_tl")
+
+    def advance_tl_device(self, a: int, cpu, mem, gpu):
+        """The tails as torch tensors resident on this GPU, n int32 entries each (all three None:
+        continue slot H - 1)."""
+        check(lib().fit_advance_tl_device(self._h, int(a), *[_ptr(t) if t is not None else None
+                                                             for t in (cpu, mem, gpu)]), "fit_advance_tl_device")
+
+    def advance_tl_ms(self):
+        """Device time in ms of the last successful advance_tl / advance_tl_device with a > 0 (HIP
+        events on the context's stream, fit_advance_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_advance_tl_ms(self._h, C.byref(ms)), "fit_advance_tl_ms")
+        return ms.value
+
     # ---- how many more copies of a job fit now (DESIGN.md §2e) ---------------------------
     def room(self, jobs):
         """Every job judged alone against the current node table (fit_room): a structured array of

@@ -46,6 +46,7 @@ EXPORTS = [
     "fit_when_k", "fit_when_k_device", "fit_when_k_ms", "fit_when_k_message",
     "fit_place_tl_k", "fit_place_tl_k_device",
     "fit_unplace_tl", "fit_unplace_tl_device", "fit_unplace_tl_ms",
+    "fit_advance_tl", "fit_advance_tl_device", "fit_advance_tl_ms",
 ]
 
 
@@ -216,6 +217,9 @@ def lib() -> C.CDLL:
         for name in ("fit_unplace_tl", "fit_unplace_tl_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, i32, P, P, C.POINTER(i64)]
         L.fit_unplace_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
+        for name in ("fit_advance_tl", "fit_advance_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P]
+        L.fit_advance_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_timeline.argtypes = [P, P, P, P]
         L.fit_ingest_nodes.argtypes = [C.c_char_p, C.c_char_p, i32, i32, P, P, P, P, P, C.c_char_p, i32]
         L.fit_expand_hostlist.argtypes = [C.c_char_p, C.c_char_p, i32]

@@ -404,6 +404,32 @@ func (e *Engine) UnplaceTL(j Jobs, kmax int, node, start []int32) (int64, error)
 	return int64(applied), check(rc)
 }
 
+// AdvanceTL moves the loaded timeline forward by a slots of slotMin minutes (DESIGN.md §2i): every
+// node's timeline shifts left by a, and the a new slots at the far end take tailCPU / tailMemMiB /
+// tailGPU of the node (caller's node order, values >= -1) wherever the node's last slot was usable:
+// per node, its total minus the demand of the running jobs that end beyond the new horizon.  All
+// three nil: every column continues its last slot, exact only when no reservation and no pending
+// release reaches the old horizon edge.  Recorded placements follow with start' = max(start-a, 0)
+// and wall' = (e-a-start')*slotMin, e = min(start+d, H); rows with e <= a are dropped.  a == 0 does
+// nothing.
+func (e *Engine) AdvanceTL(a int, tailCPU, tailMemMiB, tailGPU []int32) error {
+	if a < 0 {
+		return fmt.Errorf("fitgpu: a %d is negative", a)
+	}
+	if !sameLen(len(tailCPU), len(tailMemMiB), len(tailGPU)) {
+		return errLen
+	}
+	var tc, tm, tg *C.int32_t // NULL: continue the last slot
+	if len(tailCPU) > 0 {
+		tc = (*C.int32_t)(unsafe.Pointer(&tailCPU[0]))
+		tm = (*C.int32_t)(unsafe.Pointer(&tailMemMiB[0]))
+		tg = (*C.int32_t)(unsafe.Pointer(&tailGPU[0]))
+	}
+	rc := C.fit_advance_tl(e.ctx, C.int32_t(a), tc, tm, tg)
+	runtime.KeepAlive(e)
+	return check(rc)
+}
+
 // Eta codes (fit_eta.code, include/fitgpu.h): when a job can start.  EtaPartition .. EtaNoNodes
 // are WhyPartition .. WhyNoNodes.
 const (
