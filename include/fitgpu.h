@@ -513,6 +513,63 @@ int fit_advance_tl_device(fit_ctx* ctx, int32_t a, const int32_t* tail_cpu, cons
  * as fit_unplace_tl_ms; FIT_E_STATE before the first. */
 int fit_advance_tl_ms(fit_ctx* ctx, double* ms);
 
+/* ---- re-apply recorded reservations to the timeline -------------------------
+ * The committing mirror of fit_unplace_tl, for the placement records a caller kept across a
+ * reload (fit_load_nodes + fit_load_timeline after a resync, a dropped timeline, a restart):
+ * demand windows are SUBTRACTED from the current timeline (what fit_read_timeline returns) at their
+ * RECORDED nodes and start slots — nothing is chosen again — and the caller learns which records no
+ * longer fit.  The rows are fit_unplace_tl's, field for field: a row with start[q] < 0 is skipped
+ * whatever else it holds and gets FIT_HOLD_SKIPPED; a live row, with need = max(nodes_k, 1) and
+ * d = max(1, ceil(wall / slot_min)), covers slots [start, min(start + d, H)) of each of
+ * node[q * kmax .. + need); entries i >= need are ignored.  No partition, limit or membership test
+ * is made: the caller vouches for a record it got from a placement.
+ * Judging is ONE pass over the timeline T as the call found it, with ALL live rows of the call
+ * counted, whatever j is: S[n][t][c] is the exact sum (it does not wrap: three rows of INT32_MAX
+ * compare as larger than INT32_MAX) of the demands of all live windows that cover slot t of node n
+ * in column c; slot (n, t) is over iff S > T in any column, so a slot that reads -1 in any column
+ * (past avail_min, a column loaded negative, a node in no partition) is over for every window that
+ * covers it, a zero demand included — fit_place_tl's feasibility test, v >= demand.  A live row is
+ * refused (FIT_HOLD_REFUSED) iff any slot of any of its windows is over, else held (FIT_HOLD_HELD).
+ * There is no fixpoint: a row refused because of node A still counts on its node B and can make a
+ * row there refused too, and all parties of a conflict are refused, not the later one.  So the
+ * outcome, out_state included, does not depend on the order of the rows; the caller hands the
+ * refused rows to fit_place_tl_k, which resolves them in priority order.
+ * Only the held rows are applied: T' = T - S_held.  S_held <= S <= T on every slot a held window
+ * covers, so nothing clamps, no value goes below 0 and no -1 slot is touched.  Run lists stay
+ * canonical; cnt, head[] and the ceilings of every node a held window touches are refreshed, the
+ * ceilings exactly.  The node table (fit_read_nodes) is untouched.
+ * Replaying a placement's outputs verbatim on the timeline it started from gives, bit for bit, the
+ * timeline it ended with, every placed row held.  fit_unplace_tl of exactly the held rows restores
+ * the timeline the hold found, bit for bit.  When no row is refused, two calls give what one gives.
+ * Host pointers; nodes_k may be NULL (= all 1); *applied (may be NULL) is the sum of need over the
+ * held rows, *refused (may be NULL) the number of refused rows.  j == 0 returns 0 whatever the
+ * pointers are.
+ * FIT_E_INVAL: NULL ctx / arrays (out_state included), j < 0, kmax < 1 or kmax > FIT_MAX_K; in a
+ * live row a negative demand, need > kmax, start >= H, a node id outside [0, n) or the same node
+ * twice — the whole call fails, the timeline and out_state are unchanged (the batch is validated
+ * before the first write).
+ * FIT_E_STATE: before fit_load_nodes; without a timeline loaded; on a context created with world > 1
+ * or FIT_FLAG_COLLECTIVES.  A HIP error once writing has begun drops the timeline, as in
+ * fit_place_tl_k: FIT_E_STATE until fit_load_timeline.
+ * Bounded launches, two passes of one wave per touched node over the windows of the whole call
+ * (32 B of scratch per window); no persistent grid: the call neither takes the per-GPU
+ * persistent-launch lock nor needs the watchdog. */
+#define FIT_HOLD_HELD     1
+#define FIT_HOLD_REFUSED  0
+#define FIT_HOLD_SKIPPED (-1)
+int fit_hold_tl(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                const int32_t* wall, const uint16_t* nodes_k /* NULL = all 1 */, int32_t kmax,
+                const int32_t* node /* j * kmax */, const int32_t* start /* j */,
+                int32_t* out_state /* j */, int64_t* applied /* may be NULL */, int64_t* refused /* may be NULL */);
+/* Same with device pointers (inputs resident in HBM, out_state written in HBM); applied and refused
+ * are host pointers. */
+int fit_hold_tl_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* nodes_k, int32_t kmax, const int32_t* node,
+                       const int32_t* start, int32_t* out_state, int64_t* applied, int64_t* refused);
+/* Device time (HIP events) of the last successful fit_hold_tl / fit_hold_tl_device, as
+ * fit_unplace_tl_ms; FIT_E_STATE before the first. */
+int fit_hold_tl_ms(fit_ctx* ctx, double* ms);
+
 /* ---- how many more copies of a job fit now ---------------------------------
  * The count fit_explain does not give — "room for 12 of its 40 array tasks now", the pods a
  * partition takes of one shape, the resource that runs out first: fit_room judges each of J jobs

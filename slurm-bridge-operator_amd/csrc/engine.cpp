@@ -339,6 +339,17 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> atl_tc, atl_tm, atl_tg, atl_g;
     HBuf<int32_t> h_atl;
     double atl_ms = -1;
+    // fit_hold_tl: the staged node lists, starts and states of the host entry point, node id ->
+    // position, per-position window count / range start / scatter cursor, the touched positions, the
+    // windows of the WHOLE call, the per-row refused flags, the counters of the check (fit_unplace_tl's
+    // layout) and of the grouping (touched, handed out), the two 64-bit totals, the pinned copies, and
+    // the *_ms diagnostic
+    DBuf<int32_t> htl_node, htl_start, htl_state, htl_inv, htl_cnt, htl_first, htl_fill, htl_touched, htl_flag, htl_g;
+    DBuf<HtlWin> htl_win;
+    DBuf<unsigned long long> htl_tot;
+    HBuf<int32_t> h_htl;
+    HBuf<unsigned long long> h_htl_tot;
+    double htl_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1653,6 +1664,68 @@ int advance_tl_impl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm,
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_hold_tl
+// node id -> position and fit_unplace_tl's check of the WHOLE batch, ONE
+// synchronisation that brings back the bad-input flag and the window count — so a bad batch fails
+// before anything, out_state included, is written — then the windows of the whole call grouped by
+// node, the judge pass, the apply pass and the states with the two counts.  Bounded launches on the
+// context's stream, nothing waits on another workgroup: no launch lock, no watchdog.  Device
+// pointers; *applied and *refused (host, may be null) are valid on return.
+int hold_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                 const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
+                 int32_t* out_state, int64_t* applied, int64_t* refused) {
+    const int H = c->tl_slots;
+    hipStream_t st = c->st;
+    const int64_t nchunks = ((int64_t)J + UTL_CHUNK - 1) / UTL_CHUNK;  // of the check's window counts only
+    const size_t ng = 4 + (size_t)nchunks, np = std::max(c->nn, 1);
+    if (c->htl_inv.ensure(std::max(c->n, 1)) || c->htl_cnt.ensure(np) || c->htl_first.ensure(np) ||
+        c->htl_fill.ensure(np) || c->htl_flag.ensure(J) || c->htl_g.ensure(ng) || c->h_htl.ensure(ng) ||
+        c->htl_tot.ensure(2) || c->h_htl_tot.ensure(2))
+        return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[0], st));
+    HIP_TRY(hipMemsetAsync(c->htl_g.p, 0, sizeof(int32_t) * ng, st));
+    HIP_TRY(hipMemsetAsync(c->htl_cnt.p, 0, sizeof(int32_t) * np, st));
+    HIP_TRY(hipMemsetAsync(c->htl_flag.p, 0, sizeof(int32_t) * (size_t)J, st));
+    HIP_TRY(hipMemsetAsync(c->htl_tot.p, 0, sizeof(unsigned long long) * 2, st));
+    HIP_TRY(launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->htl_inv.p));
+    HIP_TRY(launch_utl_check(st, cpu, mem, gpu, nk, kmax, node, start, J, c->n, H, UTL_CHUNK, c->htl_g.p));
+    HIP_TRY(hipEventRecord(c->ev[1], st));
+    HIP_TRY(hipMemcpyAsync(c->h_htl.p, c->htl_g.p, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->h_htl.p[2])
+        return fail(FIT_E_INVAL, "a live row has a negative demand, nodes_k > kmax, start >= %d slots, a node id "
+                                 "outside [0, %d) or the same node twice", H, c->n);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    double dev_ms = ms;
+    int64_t total = 0;
+    for (int64_t k = 0; k < nchunks; ++k) total += c->h_htl.p[4 + k];
+    if (total > INT32_MAX) return fail(FIT_E_OOM, "%lld windows in one call", (long long)total);
+    if (c->htl_win.ensure((size_t)std::max<int64_t>(total, 1)) ||
+        c->htl_touched.ensure((size_t)std::max<int64_t>(std::min<int64_t>(total, c->nn), 1)))
+        return FIT_E_OOM;
+    HIP_TRY(hipEventRecord(c->ev[3], st));
+    // from the apply launch on the run lists may be partly written: an error drops the timeline, as
+    // in fit_place_tl_k
+    hipError_t e = launch_htl_hold(st, c->tlhdr.p, c->slab.p, c->nn, H, c->tl_slot_min, cpu, mem, gpu, wall, nk, kmax,
+                                   node, start, J, (int32_t)total, c->n, c->htl_inv.p, c->htl_cnt.p, c->htl_first.p,
+                                   c->htl_fill.p, c->htl_touched.p, c->htl_win.p, c->htl_flag.p, c->htl_g.p);
+    if (e == hipSuccess) e = launch_htl_final(st, nk, kmax, start, J, c->htl_flag.p, out_state, c->htl_tot.p);
+    if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->h_htl_tot.p, c->htl_tot.p, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+    if (e != hipSuccess) {
+        c->have_tl = false;
+        return fail(FIT_E_HIP, "fit_hold_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
+    }
+    c->htl_ms = dev_ms + ms;
+    if (applied) *applied = (int64_t)c->h_htl_tot.p[0];
+    if (refused) *refused = (int64_t)c->h_htl_tot.p[1];
+    return 0;
+}
+
 // The tests every entry point that takes a job batch makes, in the order its callers see them.
 // query: the entry point's name for fit_explain / fit_when (they also refuse j < 0 first and a
 // sharded context), nullptr for the placements.  tl: 1 a timeline must be loaded, -1 none may be.
@@ -2396,6 +2469,67 @@ int fit_unplace_tl_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->utl_ms < 0) return fail(FIT_E_STATE, "no fit_unplace_tl yet");
     *ms = c->utl_ms;
+    return 0;
+}
+
+// fit_hold_tl / fit_hold_tl_device: fit_unplace_tl's tests, out_state among the arrays; the rows
+// themselves are the device's flag word
+static int check_hold_tl_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_hold_tl", 1);
+    if (rc) return rc;
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+int fit_hold_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
+                int32_t* out_state, int64_t* applied, int64_t* refused) {
+    int rc = check_hold_tl_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (applied) *applied = 0;
+        if (refused) *refused = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t m = j, nn = (size_t)j * kmax;
+    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) || (nk && c->jk.ensure(m)) ||
+        c->htl_node.ensure(nn) || c->htl_start.ensure(m) || c->htl_state.ensure(m))
+        return FIT_E_OOM;
+    const size_t b = sizeof(int32_t) * m;
+    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
+    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, sizeof(uint16_t) * m, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->htl_node.p, node, sizeof(int32_t) * nn, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->htl_start.p, start, b, hipMemcpyHostToDevice, c->st));
+    rc = hold_tl_impl(c, j, c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, nk ? c->jk.p : nullptr, kmax, c->htl_node.p,
+                      c->htl_start.p, c->htl_state.p, applied, refused);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_state, c->htl_state.p, b, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+int fit_hold_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node,
+                       const int32_t* start, int32_t* out_state, int64_t* applied, int64_t* refused) {
+    const int rc = check_hold_tl_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax);
+    if (rc) return rc;
+    if (j == 0) {
+        if (applied) *applied = 0;
+        if (refused) *refused = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return hold_tl_impl(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, out_state, applied, refused);
+}
+
+int fit_hold_tl_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->htl_ms < 0) return fail(FIT_E_STATE, "no fit_hold_tl yet");
+    *ms = c->htl_ms;
     return 0;
 }
 

@@ -268,6 +268,24 @@ hipError_t launch_atl_check(hipStream_t st, const int32_t* tc, const int32_t* tm
 hipError_t launch_atl_advance(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t n, int32_t H, int32_t a,
                               const int32_t* tc, const int32_t* tm, const int32_t* tg);
 
+// ---- fit_hold_tl (fit_hold_tl.hip) -------------------------------------
+// The rows, their check and the node id -> position table are fit_unplace_tl's (launch_utl_check,
+// launch_utl_inverse).  The windows of the WHOLE call are grouped by node, since §2j judges per
+// call: 32 B per window.  One window of one node, with the row it belongs to:
+struct alignas(16) HtlWin {
+    int32_t s, e;           // slots [s, e), clipped to the horizon
+    int32_t cpu, mem, gpu;  // the demand to reserve
+    int32_t row;            // the row whose refused flag the window sets and obeys
+    int32_t pad[2];
+};
+hipError_t launch_htl_hold(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t H, int32_t slot_min,
+                           const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                           const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t nj,
+                           int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
+                           int32_t* fill, int32_t* touched, HtlWin* win, int32_t* flag, int32_t* g);
+hipError_t launch_htl_final(hipStream_t st, const uint16_t* jk, int32_t kmax, const int32_t* start, int32_t nj,
+                            const int32_t* flag, int32_t* out_state, unsigned long long* tot);
+
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
 enum RoomCode : int32_t {

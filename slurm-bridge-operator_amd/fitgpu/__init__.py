@@ -36,7 +36,8 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
                    FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta, FitEtaK, FIT_MAX_K,
                    FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
-                   FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom)
+                   FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom,
+                   FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -53,6 +54,7 @@ __all__ = [
     "when_k_message", "ETA_K_DTYPE", "FitEtaK", "FIT_MAX_K",
     "room_message", "ROOM_DTYPE", "FitRoom", "FIT_ROOM_SOME", "FIT_ROOM_PARTITION", "FIT_ROOM_LIMIT_TIME",
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
+    "FIT_HOLD_HELD", "FIT_HOLD_REFUSED", "FIT_HOLD_SKIPPED",
 ]
 
 
@@ -747,6 +749,48 @@ class Engine:
         events on the context's stream, fit_advance_tl_ms)."""
         ms = C.c_double()
         check(lib().fit_advance_tl_ms(self._h, C.byref(ms)), "fit_advance_tl_ms")
+        return ms.value
+
+    # ---- re-apply recorded reservations to the timeline (DESIGN.md §2j) ----------------------
+    def hold_tl(self, jobs, node, start, kmax: int | None = None):
+        """Subtract the rows' demand windows from the current timeline at their recorded nodes and
+        start slots (fit_hold_tl), unless they no longer fit: jobs, node[J, kmax] (or node[J] at kmax 1)
+        and start[J] as unplace_tl takes them; rows with start < 0 are skipped, so a placement's outputs
+        go in verbatim.  kmax None: node's second dimension (1 for a flat array).  Returns (state[J]
+        of FIT_HOLD_HELD / FIT_HOLD_REFUSED / FIT_HOLD_SKIPPED, the nodes of the held rows, the
+        refused rows)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        node = np.ascontiguousarray(node, np.int32)
+        start = np.ascontiguousarray(start, np.int32)
+        j = len(start)
+        if kmax is None:
+            kmax = node.shape[1] if node.ndim == 2 else 1
+        # a kmax outside 1..FIT_MAX_K is the library's error (FIT_E_INVAL), before it reads node
+        if any(len(c) != j for c in cols) or len(k) != j or (1 <= kmax <= FIT_MAX_K and node.size != j * kmax):
+            raise ValueError("jobs, node (J * kmax) and start (J) disagree on J")
+        state = np.full(j, FIT_HOLD_SKIPPED, np.int32)
+        applied, refused = C.c_int64(), C.c_int64()
+        check(lib().fit_hold_tl(self._h, j, *[_ptr(c) for c in cols], _ptr(k), int(kmax), _ptr(node), _ptr(start),
+                                _ptr(state), C.byref(applied), C.byref(refused)), "fit_hold_tl")
+        return state, applied.value, refused.value
+
+    def hold_tl_device(self, cpu, mem, gpu, wall, nodes_k, node, start, out_state, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1; node has
+        J * kmax int32 entries); writes out_state (J int32).  Returns (the nodes of the held rows, the
+        refused rows)."""
+        applied, refused = C.c_int64(), C.c_int64()
+        check(lib().fit_hold_tl_device(self._h, int(start.numel()), _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
+                                       _ptr(nodes_k) if nodes_k is not None else None, int(kmax), _ptr(node),
+                                       _ptr(start), _ptr(out_state), C.byref(applied), C.byref(refused)),
+              "fit_hold_tl_device")
+        return applied.value, refused.value
+
+    def hold_tl_ms(self):
+        """Device time in ms of the last successful hold_tl / hold_tl_device (HIP events on the
+        context's stream, fit_hold_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_hold_tl_ms(self._h, C.byref(ms)), "fit_hold_tl_ms")
         return ms.value
 
     # ---- how many more copies of a job fit now (DESIGN.md §2e) ---------------------------

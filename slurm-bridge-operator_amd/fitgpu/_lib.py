@@ -47,6 +47,7 @@ EXPORTS = [
     "fit_place_tl_k", "fit_place_tl_k_device",
     "fit_unplace_tl", "fit_unplace_tl_device", "fit_unplace_tl_ms",
     "fit_advance_tl", "fit_advance_tl_device", "fit_advance_tl_ms",
+    "fit_hold_tl", "fit_hold_tl_device", "fit_hold_tl_ms",
 ]
 
 
@@ -78,6 +79,7 @@ class FitStats(C.Structure):
 
 
 FIT_MAX_K = 8
+FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED = 1, 0, -1
 
 
 class FitAdmitReq(C.Structure):
@@ -220,6 +222,9 @@ def lib() -> C.CDLL:
         for name in ("fit_advance_tl", "fit_advance_tl_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P]
         L.fit_advance_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
+        for name in ("fit_hold_tl", "fit_hold_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, i32, P, P, P, C.POINTER(i64), C.POINTER(i64)]
+        L.fit_hold_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_timeline.argtypes = [P, P, P, P]
         L.fit_ingest_nodes.argtypes = [C.c_char_p, C.c_char_p, i32, i32, P, P, P, P, P, C.c_char_p, i32]
         L.fit_expand_hostlist.argtypes = [C.c_char_p, C.c_char_p, i32]

@@ -404,6 +404,48 @@ func (e *Engine) UnplaceTL(j Jobs, kmax int, node, start []int32) (int64, error)
 	return int64(applied), check(rc)
 }
 
+// Hold states (out_state of fit_hold_tl, include/fitgpu.h).
+const (
+	HoldHeld    = int32(C.FIT_HOLD_HELD)
+	HoldRefused = int32(C.FIT_HOLD_REFUSED)
+	HoldSkipped = int32(C.FIT_HOLD_SKIPPED)
+)
+
+// HoldTL re-applies recorded reservations to the loaded timeline (DESIGN.md §2j), after a reload,
+// a dropped timeline or a restart: row q subtracts its per-node demand from slots [start[q],
+// start[q]+d) of node[q*kmax .. +max(NodesK,1)) — the recorded nodes and start, nothing is chosen
+// again — unless on one of those slots the demands of all live rows of the call together exceed
+// what the timeline holds; then every row that covers the slot is refused and nothing of it is
+// subtracted.  j, node and start are UnplaceTL's; rows with start[q] < 0 are skipped.  j.Part is not
+// used.  Returns the state of every row (HoldHeld, HoldRefused, HoldSkipped), the nodes of the held
+// rows and the number of refused rows; the refused rows go to PlaceTLK.
+func (e *Engine) HoldTL(j Jobs, kmax int, node, start []int32) ([]int32, int64, int64, error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return nil, 0, 0, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(start)) || len(node) != cnt*kmax ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, 0, 0, errLen
+	}
+	state := make([]int32, cnt)
+	if cnt == 0 {
+		return state, 0, 0, nil
+	}
+	var nk *C.uint16_t // NULL: every job took one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	var applied, refused C.int64_t
+	rc := C.fit_hold_tl(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), nk, C.int32_t(kmax),
+		(*C.int32_t)(unsafe.Pointer(&node[0])), (*C.int32_t)(unsafe.Pointer(&start[0])),
+		(*C.int32_t)(unsafe.Pointer(&state[0])), &applied, &refused)
+	runtime.KeepAlive(e)
+	return state, int64(applied), int64(refused), check(rc)
+}
+
 // AdvanceTL moves the loaded timeline forward by a slots of slotMin minutes (DESIGN.md §2i): every
 // node's timeline shifts left by a, and the a new slots at the far end take tailCPU / tailMemMiB /
 // tailGPU of the node (caller's node order, values >= -1) wherever the node's last slot was usable:
