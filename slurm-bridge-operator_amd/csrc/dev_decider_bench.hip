@@ -32,7 +32,7 @@ __global__ __launch_bounds__(64) void k_dec_bench(int w, int32_t* out, unsigned 
     P.ne = 2048;
     P.w = w;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    const CommitResult r = mw_decider(P, S, out, 1);
+    const CommitResult r = mw_decider<false>(P, S, out, 1);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (lane == 0) {
         cyc[0] = t1 - t0;

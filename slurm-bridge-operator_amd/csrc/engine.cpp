@@ -388,6 +388,7 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> jcpu, jmem, jgpu, jwall, out, jl, jpk;
     DBuf<uint16_t> jpart, jk;
     DBuf<int8_t> jcomp;
+    DBuf<int32_t> jmin;  // per-component minimum demands of the placement's jobs (k_prefilter)
     DBuf<uint64_t> cand, bnd;
     DBuf<JobRec> wjob;
     DBuf<CompPlan> plan;
@@ -736,6 +737,9 @@ int run_persistent(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector
     if (const char* e = getenv("FIT_WORKERS")) workers = std::max(1, atoi(e));
     // the node rows as they were: a trip leaves them partly committed, and the context must stay
     // usable after FIT_E_HIP (restored below)
+    EngineCompIds ids;  // launch component -> component id (the rows of jmin)
+    memset(&ids, 0, sizeof ids);
+    for (int i = 0; i < nc; ++i) ids.id[i] = (int8_t)E.comps[i];
     static const bool no_backup = getenv("FIT_REC_BACKUP") && atoi(getenv("FIT_REC_BACKUP")) == 0;  // A/B only
     if (c->rec_bak.ensure(std::max(c->nn, 1))) return FIT_E_OOM;
     if (!no_backup)
@@ -746,7 +750,7 @@ int run_persistent(fit_ctx* c, const std::vector<int32_t>& jb, const std::vector
             HIP_TRY(launch_engine(nc + workers, lds, st, c->ectl.p, c->ering.p, c->ecs.p, c->eco.p,
                                   c->plan.p, nc, c->rec.p, c->jl.p, cpu, mem, gpu, wall, part, nk,
                                   c->cand.p, c->bnd.p, c->wjob.p, out, kmax, c->ebusy.p, c->jpk.p,
-                                  c->wd_ticks));
+                                  c->wd_ticks, c->jmin.p, ids));
             return 0;
         },
         [&](int trip) -> int {
@@ -1054,9 +1058,11 @@ int place_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, co
         return 0;
     }
     // 1. prefilter: out[] init, FIT_REJECTED, component per job
-    if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
+    // (and each component's minimum demands, for the persistent engine's recycling)
+    if (c->jcomp.ensure(std::max(J, 1)) || c->jmin.ensure(3 * ENGINE_MAXC)) return FIT_E_OOM;
+    HIP_TRY(hipMemsetAsync(c->jmin.p, JMIN_FILL, sizeof(int32_t) * 3 * ENGINE_MAXC, st));
     HIP_TRY(launch_prefilter(st, cpu, mem, gpu, wall, part, nk, J, kmax, c->d_ptab.p, c->np, out,
-                             c->jcomp.p));
+                             c->jcomp.p, c->jmin.p));
     // 2. per-component job lists in priority order (stable)
     const int C = c->ncomp;
     std::vector<int32_t> jb;

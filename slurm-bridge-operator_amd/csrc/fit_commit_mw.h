@@ -79,11 +79,36 @@ static_assert(MW_R >= MW_M, "record slot reuse relies on the lag bound");
 constexpr int MW_EPL = (MAX_SLICES * KS + 63) / 64;  // candidate entries per helper lane
 static_assert(MW_EPL <= 2, "at most two candidate entries per lane");
 
+// The dirty set of this commit (DESIGN.md §3.7 "recycling"), chosen per component at launch
+// (MwShared::ucap):
+//   MW_UCAP = 64 rows, one per helper lane (3 entries per lane with the candidates), with
+//     recycling: when the set is full the decider RETIRES a row that fits no job of the component
+//     any more (below the component's minimum demand in one resource; resources only shrink) — its
+//     values wait in retired[] for the round's write-back and the fresh node takes its slot — up
+//     to MW_RCAP rows a round;
+//   UCAP = 128 rows, two per helper lane, a full set stops the round: components whose round
+//     start is dear (k_engine: those scanned with fewer keys per slice), where rounds count more
+//     than the helpers' entries (C3o).
+// UCAP is also the capacity of the single-wave commit and the host-driven rounds (fit_common.h).
+constexpr int MW_UCAP = 64;
+#ifndef MW_RETIRE
+#define MW_RETIRE 128  // 0: a full set always stops the round (no recycling)
+#endif
+constexpr int MW_RCAP = MW_RETIRE;
+static_assert(UCAP == 2 * MW_UCAP, "retired[] lies over the rows a 64-row set leaves unused");
+static_assert(MW_RCAP * 16 <= (UCAP - MW_UCAP) * 32, "retired[] fits there");
+static_assert(MW_UCAP + MW_RCAP < 256, "a 256-job window of fresh nodes still fills the set");
+
 struct alignas(16) MwRow {  // dirty row, current state
     int32_t cpu, mem, gpu, avail;
     uint32_t mask, pos;
     int32_t orig, ver;  // ver: last job (record index) that created or changed it; read back by
                         // the decider's staleness probe of a dirty item
+};
+
+struct alignas(16) MwRet {  // a retired row: what the round's write-back stores
+    uint32_t pos;
+    int32_t cpu, mem, gpu;
 };
 
 struct alignas(16) MwItem {  // 48 B, read whole by the decider (three 16-B reads)
@@ -122,11 +147,20 @@ struct alignas(16) MwShared {
     uint32_t wd;       // watchdog: realtime ticks a wait may last (set by the committer; the
                        // commit's own waits use spin bounds, see MW_SPIN_LIMIT)
     uint32_t trip_arg; // the failed wait's tile / record
-    uint32_t pad[5];
+    uint32_t pad[1];   // the sink of an unwritten item's staleness probe (mw_reset_items)
+    uint32_t nret;     // rows in retired[] this round (set by the decider at its end)
+    int32_t mind[3];   // the component's minimum cpu / mem / gpu demand over its non-rejected jobs
+                       // (set by the committer at launch): a row below one of them is dead
+    uint32_t ucap;     // dirty capacity of this component's commits: MW_UCAP (recycling) or UCAP
+    uint32_t pad1[1];
     MwRec rec[MW_R];
-    MwRow rows[UCAP];
+    MwRow rows[UCAP];  // ucap == MW_UCAP: rows[MW_UCAP ..) hold retired[] (mw_retired)
     uint32_t bitmap[1];  // (ne - nb + 31) / 32 words, dirty membership by position
 };
+
+__device__ __forceinline__ MwRet* mw_retired(MwShared* S) {
+    return reinterpret_cast<MwRet*>(&S->rows[MW_UCAP]);
+}
 
 __host__ __device__ constexpr size_t mw_lds_bytes(int32_t max_component_nodes) {
     return sizeof(MwShared) + (size_t)((max_component_nodes + 31) / 32) * 4;
@@ -553,9 +587,9 @@ __device__ __forceinline__ MwTiles tiles_sgpr(const MwTiles& T) {
 // ------------------------------------------------------------------------------- helper
 // Helper entry lists: MW_EPL clean candidates + UPL dirty rows per lane, each key tagged with
 // its entry index in the low bits (positions < 2^29, FIT_MAX_NODES), INF stays INF.
-constexpr int UPL_MW = UCAP / 64;
-constexpr int MW_NE = MW_EPL + UPL_MW;
-static_assert(MW_NE <= 8, "entry index takes 3 bits (and 4 bits of item index each in 32)");
+// (UPL_MW = dirty rows per lane, 1 or 2, and MW_NE = MW_EPL + UPL_MW are mw_helper's template
+// constants; the macros below use them by name)
+static_assert(MW_EPL + UCAP / 64 <= 8, "entry index takes 3 bits (and 4 bits of item index each in 32)");
 static_assert(MW_M <= 15, "item index + 1 fits 4 bits");
 __device__ __forceinline__ uint64_t mw_tag(uint64_t k, int e) {
     return k == KEY_INF ? KEY_INF
@@ -776,11 +810,13 @@ __device__ __forceinline__ uint32_t wave_min32_all(uint32_t v) {
         i += MW_H;                                                                             \
     }
 
+template <int UPL_MW>
 __device__ __noinline__ void mw_helper(const CompPlan& Pref, MwShared* Sin,
                                        const NodeRec* __restrict__ rec_,
                                        const uint64_t* __restrict__ cand_,
                                        const uint64_t* __restrict__ bnd_,
                                        const JobRec* __restrict__ wjob_, int h, MwTiles Tin) {
+    constexpr int MW_NE = MW_EPL + UPL_MW;
     const MwTiles T = tiles_sgpr(Tin);
     const GAS NodeRec* const rec = gview(rec_);
     const GAS uint64_t* const cand = gview(cand_);
@@ -879,6 +915,8 @@ struct MwDec {
     int t, nu, placed, stop;  // t: records decided (live jobs)
     int done;                 // window jobs resolved when the walk ended (its stop / end record)
     bool exit;  // the window is finished (end, stop or watchdog): later steps change nothing
+    int nret;       // rows appended to retired[] this round
+    uint64_t dead;  // slots found dead (and listed in retired[]) whose slot is not reused yet
 #ifdef MW_SEGSTAMP
     unsigned long long seg[8], prev;
 #endif
@@ -930,13 +968,69 @@ __device__ __forceinline__ void mw_reset_items(MwShared* S, unsigned tid) {
         *reinterpret_cast<v4u32*>(&S->rec[i / MW_M].it[i % MW_M].mask) = v4u32{0u, sink, 0u, 0u};
 }
 
+// The decider's dirty set is full and job t's winner is a fresh node at position `pos` (uniform;
+// the step's exception path only).  Returns the slot of a dead row — one with less than the
+// component's minimum demand in one resource — after setting the fresh node's bitmap bit; the
+// step's apply path then rewrites the slot with ver = t.  -1: no row is dead, or the round's
+// retired list is full.
+// The dead slots come from one pass over the rows (one per lane, one ballot), kept in D.dead (an
+// SGPR pair) and used bit by bit; the pass runs again only when they are used up.  The pass also
+// appends every dead row it keeps to retired[] (a masked store per lane, nothing to wait for), so
+// taking a slot later reads nothing: a dead row never changes again, and one that is still in
+// rows[] at the round's end is written back from both places with the same values.
+// Why it is exact: the retired node keeps its bitmap bit, so no clean list offers
+// it, and it fits no job of the component, so leaving the set changes no decision (its ring entry
+// evaluates to KEY_INF); an item of a record in flight that names the slot is dropped by its probe
+// (ver = t >= its snapshot), and the fresh node is in the live ring of every such record.
+__device__ __forceinline__ int mw_recycle(MwShared* S, const CompPlan& P, MwDec& D, uint32_t pos) {
+    if (D.dead == 0ull) {  // uniform
+        const int room = MW_RCAP - D.nret;
+        if (room <= 0) return -1;
+        const int lane = threadIdx.x & 63;
+        const MwRow r = S->rows[lane];  // all MW_UCAP = 64 rows exist: the set is full
+        const int32_t mc = S->mind[0], mm = S->mind[1], mg = S->mind[2];
+        const uint64_t all = __ballot(r.cpu < mc || r.mem < mm || r.gpu < mg);
+        // the first `room` of them
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(all >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)all, 0u));
+        const bool mine = ((all >> lane) & 1ull) && rank < room;
+        const uint64_t dm = __ballot(mine);
+        if (dm == 0ull) return -1;
+        if (mine) mw_retired(S)[D.nret + rank] = MwRet{r.pos, r.cpu, r.mem, r.gpu};
+        D.nret += (int)__builtin_popcountll(dm);
+        D.dead = dm;
+        // drained here, once per pass: left pending, the stores make the compiler wait before the
+        // next record's reads on the step's straight line
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+    }
+    const int s = (int)__builtin_ctzll(D.dead);
+    D.dead &= D.dead - 1ull;
+    {  // the fresh node's bitmap bit, by one lane (as the apply path's bookkeeping does)
+        const uint32_t rel = pos - (uint32_t)P.nb;
+        const uint32_t ba = mw_lds_addr(&S->bitmap[rel >> 5]);
+        const uint32_t bv = 1u << (rel & 31);
+        uint64_t sv;
+        asm volatile(
+            "s_mov_b64 %[sv], exec\n\t"
+            "s_mov_b64 exec, 1\n\t"
+            "ds_or_b32 %[ba], %[bv]\n\t"
+            "s_mov_b64 exec, %[sv]"
+            : [sv] "=&s"(sv)
+            : [ba] "v"(ba), [bv] "v"(bv)
+            : "memory");
+    }
+    return s;
+}
+
 // One job of the decider: job D.t with record `cur` (its data read after an acquire of the ready
 // word `flag`; refreshed in place on the slow path), `nxt` receives record t+1.  E = t & 7 is a
 // compile-time constant.  Straight-line: the decision is computed unconditionally and selected (no
 // exec-masked region), its bookkeeping is masked with `go` instead of branched around, and the
 // only branch is the rare exception (record not ready, B exceeded, dirty set full).  Once D.exit
 // is set the step has no effect: the caller tests it once per 8 jobs.
-template <int E>
+// RC: the 64-row set with recycling (MwShared::ucap == MW_UCAP); else UCAP rows and the
+// parent's code, instruction for instruction.
+template <int E, bool RC>
 __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec& D, MwRing& R,
                                           MwRecRegs& cur, MwRecRegs& nxt, uint32_t& flag,
                                           int32_t& oq, int32_t& ov, int32_t* out, int kmax,
@@ -1010,7 +1104,7 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         d.placed = d.bs != KEY_INF;
         d.wslot = readlane(d.ss, d.w);
         d.fresh = d.placed && d.wslot < 0;
-        d.full = d.fresh && D.nu >= UCAP;
+        d.full = d.fresh && D.nu >= (RC ? MW_UCAP : UCAP);
         d.stopB = B != KEY_INF && d.bs > B;
         return d;
     };
@@ -1042,6 +1136,18 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
                 MW_ACC(waitcyc, c1 - c0);
             }
             d = decide(cur);
+        }
+        // the dirty set is full: a dead row's slot takes the fresh node (mw_recycle), and the step
+        // goes on as if the node had been dirty in that slot
+        if constexpr (RC && MW_RCAP > 0) {
+            if (!D.exit && d.full && !d.stopB) {
+                const int s = mw_recycle(S, P, D, (uint32_t)d.bs);
+                if (s >= 0) {
+                    d.wslot = s;
+                    d.fresh = false;
+                    d.full = false;
+                }
+            }
         }
         if (!D.exit && (d.stopB || d.full)) {
             // the end record (no live job left: B = 0, nothing fits) or a stop at the record's
@@ -1118,13 +1224,14 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
 
 // Out of line (as is mw_helper): called once per round, each gets its own register allocation
 // instead of sharing the persistent kernel's (which otherwise spills SGPRs in this loop).
+template <bool RC>
 __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* Sin,
                                                 int32_t* __restrict__ out, int kmax) {
     const CompPlan P = plan_sgpr(Pref);  // by value (see mw_helper)
     MwShared* const S = lds_opaque(Sin);
     const int lane = threadIdx.x & 63;
     __builtin_amdgcn_s_setprio(3);  // shares its SIMD with a helper wave
-    MwDec D{0, 0, 0, 0, 0, false};
+    MwDec D{0, 0, 0, 0, 0, false, 0, 0ull};
 #ifdef MW_SEGSTAMP
     for (int i = 0; i < 8; ++i) D.seg[i] = 0;
     D.prev = 0;
@@ -1167,14 +1274,14 @@ __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* 
     // 8-way unrolled: the ring lane (t & 7) is a constant in every step; the two record register
     // sets alternate with the step's parity; the exit is tested once per 8 steps
     while (!D.exit) {
-        mw_decide<0>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<1>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<2>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<3>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<4>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<5>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<6>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<7>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<0, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<1, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<2, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<3, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<4, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<5, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<6, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<7, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
     }
     const int t = D.t;
     if (oq >= 0 && lane < (t & 63)) ((GAS int32_t*)out)[(int64_t)oq * kmax] = ov;  // last group
@@ -1182,6 +1289,7 @@ __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* 
     lds_release();
     __hip_atomic_store(&S->dn, ((uint64_t)(uint32_t)D.nu << 32) | (uint32_t)t, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_WORKGROUP);
+    lds_st(&S->nret, (uint32_t)D.nret);
     lds_st(&S->halt, 1u);
     MW_CLK(d1);
     MW_ADD(0, d1 - d0);
@@ -1214,10 +1322,13 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
         S->dn = 0ull;
         S->halt = 0u;
         S->fail = 0u;
+        S->nret = 0u;
     }
     __syncthreads();
     if (wave == 0) {
-        const CommitResult r = mw_decider(P, S, out, kmax);
+        // block-uniform: the 64-row set with recycling, or UCAP rows
+        const CommitResult r = S->ucap == (uint32_t)MW_UCAP ? mw_decider<true>(P, S, out, kmax)
+                                                            : mw_decider<false>(P, S, out, kmax);
         if (threadIdx.x == 0) {
             S->res[0] = r.done;
             S->res[1] = r.stop;
@@ -1225,7 +1336,9 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
             S->res[3] = r.placed;
         }
     } else {
-        mw_helper(P, S, rec, cand, bnd, wjob, wave, T);  // waves 1.. : helpers 1..MW_H
+        // waves 1.. : helpers 1..MW_H, with one or two dirty rows per lane (block-uniform)
+        if (S->ucap == (uint32_t)MW_UCAP) mw_helper<1>(P, S, rec, cand, bnd, wjob, wave, T);
+        else mw_helper<2>(P, S, rec, cand, bnd, wjob, wave, T);
     }
     __syncthreads();
     const CommitResult r{S->res[0], S->res[1], S->res[2], S->res[3]};
@@ -1233,6 +1346,15 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
     // publish needs no release fence for them; {cpu, mem} as one 8-B word, then gpu)
     for (int u = threadIdx.x; u < r.dirty; u += MW_WAVES * 64) {
         const MwRow w = S->rows[u];
+        NodeRec* d = rec + w.pos;
+        __hip_atomic_store(reinterpret_cast<uint64_t*>(&d->cpu),
+                           (uint64_t)(uint32_t)w.cpu | ((uint64_t)(uint32_t)w.mem << 32),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&d->gpu, w.gpu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the rows retired this round: no other row of the round names their nodes
+    for (int u = threadIdx.x; u < (int)S->nret; u += MW_WAVES * 64) {
+        const MwRet w = mw_retired(S)[u];
         NodeRec* d = rec + w.pos;
         __hip_atomic_store(reinterpret_cast<uint64_t*>(&d->cpu),
                            (uint64_t)(uint32_t)w.cpu | ((uint64_t)(uint32_t)w.mem << 32),

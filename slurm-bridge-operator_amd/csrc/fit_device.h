@@ -87,6 +87,15 @@ struct CompState {
     int32_t pair_off;      // half-slice list scratch (even rounds; odd: + PAIR_AREA)
 };
 
+// Per-component minimum demands (k_prefilter → k_engine's committers, DESIGN.md §3.7 recycling):
+// jmin[3 * k + {0, 1, 2}] = the smallest cpu / mem / gpu demand among component k's non-rejected
+// jobs, preset to JMIN_FILL bytes (0x7f7f7f7f: a component without jobs) before the prefilter.
+constexpr int ENGINE_MAXC = 32;   // components (one per partition at most)
+constexpr int JMIN_FILL = 0x7f;   // memset byte of the preset
+struct EngineCompIds {            // launch component i of the persistent engine = component id[i]
+    int8_t id[ENGINE_MAXC];
+};
+
 struct CompOut {
     int64_t evals, placed, done_jobs, rounds, stops_rescan, stops_dirty;
     int64_t t_commit, t_wait;  // 100 MHz realtime ticks spent committing / waiting for scans
@@ -339,7 +348,7 @@ hipError_t launch_commit(int ncomp, int epl, size_t lds_bytes, hipStream_t st, N
 hipError_t launch_prefilter(hipStream_t st, const int32_t* jcpu, const int32_t* jmem,
                             const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
                             int32_t nj, int32_t kmax, const int32_t* ptab, int32_t np,
-                            int32_t* out, int8_t* jcomp);
+                            int32_t* out, int8_t* jcomp, int32_t* jmin = nullptr);
 size_t joblists_scratch_ints(int32_t nj);
 hipError_t launch_joblists(hipStream_t st, const int8_t* jcomp, int32_t nj, int ncomp,
                            int32_t* scratch, int32_t* g, int32_t* jb, int32_t* mb, int32_t* jl,
@@ -383,7 +392,8 @@ hipError_t launch_engine(int blocks, size_t lds, hipStream_t st, void* ctl, void
                          const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
                          const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                          const uint16_t* jk, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
-                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd);
+                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd,
+                         const int32_t* jmin, const EngineCompIds& ids);
 // time-windowed backfill (fit_timeline.hip)
 hipError_t launch_build_tl(hipStream_t st, const int32_t* cpu, const int32_t* mem,
                            const int32_t* gpu, const int32_t* av, const uint32_t* mask,

@@ -72,17 +72,48 @@ __device__ __forceinline__ int job_code(int q, const int32_t* __restrict__ jcpu,
     return comp;
 }
 
-__global__ void k_prefilter(const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem,
-                            const int32_t* __restrict__ jgpu, const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart,
-                            const uint16_t* __restrict__ jk, int32_t nj, int32_t kmax,
-                            const int32_t* __restrict__ ptab /* [4][32]: time,cpus,mem,comp */,
-                            int32_t np, int32_t* __restrict__ out, int8_t* __restrict__ jcomp) {
+// MIN: also the smallest cpu / mem / gpu demand of each component's non-rejected jobs into
+// jmin[3 * component + r] (fit_device.h; the persistent engine's recycling reads them): LDS
+// minima per block, then one global atomicMin per (block, word) that still lowers the word —
+// the minima settle within the first blocks, so almost every later block only reads.
+template <bool MIN>
+__global__ __launch_bounds__(256) void k_prefilter(
+    const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem,
+    const int32_t* __restrict__ jgpu, const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart,
+    const uint16_t* __restrict__ jk, int32_t nj, int32_t kmax,
+    const int32_t* __restrict__ ptab /* [4][32]: time,cpus,mem,comp */,
+    int32_t np, int32_t* __restrict__ out, int8_t* __restrict__ jcomp, int32_t* __restrict__ jmin) {
+    __shared__ int32_t smin[MIN ? 3 * ENGINE_MAXC : 1];
+    if constexpr (MIN) {
+        if (threadIdx.x < 3 * ENGINE_MAXC) smin[threadIdx.x] = INT32_MAX;
+        __syncthreads();
+    }
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nj) return;
-    bool rej;
-    int k;
-    jcomp[q] = (int8_t)job_code(q, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, ptab, np, &rej, &k);
-    for (int i = 0; i < kmax; ++i) out[(int64_t)q * kmax + i] = (rej && i < k) ? -2 : -1;
+    if (q < nj) {
+        bool rej;
+        int k;
+        const int code = job_code(q, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, ptab, np, &rej, &k);
+        jcomp[q] = (int8_t)code;
+        for (int i = 0; i < kmax; ++i) out[(int64_t)q * kmax + i] = (rej && i < k) ? -2 : -1;
+        if constexpr (MIN) {
+            if (code >= 0) {
+                const int cc = code & 0x3f;
+                atomicMin(&smin[3 * cc], jcpu[q]);
+                atomicMin(&smin[3 * cc + 1], jmem[q]);
+                atomicMin(&smin[3 * cc + 2], jgpu ? jgpu[q] : 0);
+            }
+        }
+    }
+    if constexpr (MIN) {
+        __syncthreads();
+        if (threadIdx.x < 3 * ENGINE_MAXC) {
+            const int32_t v = smin[threadIdx.x];
+            // the word only falls: a stale (higher) read costs one atomic, never a missed minimum
+            if (v != INT32_MAX &&
+                v < __hip_atomic_load(&jmin[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicMin(&jmin[threadIdx.x], v);
+        }
+    }
 }
 
 __global__ void k_gather_nodes(const int32_t* __restrict__ cpu, const int32_t* __restrict__ mem,
@@ -124,7 +155,7 @@ __global__ void k_scatter_nodes(const NodeRec* __restrict__ rec, int32_t nn,
 // exclusive scan over blocks per component, and the scatter (block offset + wave offset + lane
 // rank), so the order inside each component is the caller's.
 constexpr int JL_BLOCK = 1024;
-constexpr int JL_MAXC = 32;
+constexpr int JL_MAXC = ENGINE_MAXC;
 
 __global__ __launch_bounds__(JL_BLOCK) void k_jl_count(const int8_t* __restrict__ jcomp, int32_t nj,
                                                        int ncomp, int32_t* __restrict__ bc,
@@ -594,10 +625,14 @@ extern "C" int fit_debug_commit_stamps(unsigned long long* out /* 64 x 8 */) {
 hipError_t launch_prefilter(hipStream_t st, const int32_t* jcpu, const int32_t* jmem,
                             const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart, const uint16_t* jk,
                             int32_t nj, int32_t kmax, const int32_t* ptab, int32_t np,
-                            int32_t* out, int8_t* jcomp) {
+                            int32_t* out, int8_t* jcomp, int32_t* jmin) {
     if (nj == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_prefilter, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall,
-                       jpart, jk, nj, kmax, ptab, np, out, jcomp);
+    if (jmin)
+        hipLaunchKernelGGL(k_prefilter<true>, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu,
+                           jwall, jpart, jk, nj, kmax, ptab, np, out, jcomp, jmin);
+    else
+        hipLaunchKernelGGL(k_prefilter<false>, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu,
+                           jwall, jpart, jk, nj, kmax, ptab, np, out, jcomp, jmin);
     return hipGetLastError();
 }
 

@@ -79,7 +79,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine(
     const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk,
     uint64_t* __restrict__ cand, uint64_t* __restrict__ bnd, JobRec* __restrict__ wjob,
     int32_t* __restrict__ out, int kmax, int64_t* __restrict__ wbusy,
-    const int32_t* __restrict__ jpk, unsigned wd) {
+    const int32_t* __restrict__ jpk, unsigned wd, const int32_t* __restrict__ jmin,
+    const EngineCompIds ids) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     if (threadIdx.x == 0) stamp_start(ctl);
@@ -93,7 +94,19 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine(
         const int c = blockIdx.x;
         const CompState S = cs[c];
         MwShared* M = reinterpret_cast<MwShared*>(smem);
-        if (threadIdx.x == 0) M->wd = wd;  // the commit waits' deadline (fit_commit_mw.h)
+        if (threadIdx.x == 0) {
+            M->wd = wd;  // the commit waits' deadline (fit_commit_mw.h)
+            // the component's minimum demands (k_prefilter), read once: a dirty row below one of
+            // them fits none of its jobs and may be retired (fit_commit_mw.h mw_recycle)
+            const int32_t* mn = jmin + 3 * ids.id[c];
+            M->mind[0] = mn[0];
+            M->mind[1] = mn[1];
+            M->mind[2] = mn[2];
+            // 64 dirty rows with recycling where a round start is cheap; a component scanned with
+            // fewer keys per slice (its sub-slices would exceed the target: > 16k nodes) pays its
+            // round starts dearly and keeps 128 rows (C3o: 837 rounds against 1,100)
+            M->ucap = S.ks == KS ? (uint32_t)MW_UCAP : (uint32_t)UCAP;
+        }
         int32_t cursor = S.jstart, win = S.wmin;
         unsigned target[2] = {0u, 0u};  // tiles published by the rounds of each parity
         // job tiles published by the last round of each parity: only their bounds can differ from
@@ -429,12 +442,13 @@ hipError_t launch_engine(int blocks, size_t lds, hipStream_t st, void* ctl, void
                          const int32_t* jl, const int32_t* jcpu, const int32_t* jmem,
                          const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                          const uint16_t* jk, uint64_t* cand, uint64_t* bnd, JobRec* wjob,
-                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd) {
+                         int32_t* out, int kmax, int64_t* wbusy, const int32_t* jpk, unsigned wd,
+                         const int32_t* jmin, const EngineCompIds& ids) {
     hipLaunchKernelGGL(k_engine, dim3(blocks), dim3(SCAN_WAVES * 64), lds, st,
                        static_cast<EngineCtl*>(ctl), static_cast<unsigned long long*>(ring),
                        static_cast<const CompState*>(cs), static_cast<CompOut*>(co), plans, ncomp,
                        rec, jl, jcpu, jmem, jgpu, jwall, jpart, jk, cand, bnd, wjob, out, kmax,
-                       wbusy, jpk, wd);
+                       wbusy, jpk, wd, jmin, ids);
     return hipGetLastError();
 }
 
