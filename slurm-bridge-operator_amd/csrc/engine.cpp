@@ -326,30 +326,24 @@ struct fit_ctx : CtxHandles {
     // fit_place_tl_k: the placed count of the commit launches (device, pinned)
     DBuf<int32_t> ptlk_cnt;
     HBuf<int32_t> h_ptlk;
-    // fit_unplace_tl: the staged node lists and starts of the host entry point, node id -> position,
-    // per-position window count / range start / scatter cursor, the touched positions and the
-    // windows of one chunk, the counters (touched, handed out, bad flag, pad, windows per chunk) with
-    // their pinned copy, and the *_ms diagnostic
-    DBuf<int32_t> utl_node, utl_start, utl_inv, utl_cnt, utl_first, utl_fill, utl_touched, utl_g;
-    DBuf<UtlWin> utl_win;
-    HBuf<int32_t> h_utl;
-    double utl_ms = -1;
+    // fit_unplace_tl and fit_hold_tl, ONE set between them: the staged node lists, starts and (hold)
+    // states of the host entry points, node id -> position, per-position window count / range start /
+    // scatter cursor, the touched positions and the windows of one grouping (a chunk of fit_unplace_tl,
+    // the whole call of fit_hold_tl: each call sizes them), hold's per-row refused flags and two
+    // 64-bit totals, the counter words (fit_device.h) and the pinned copies.
+    // Sharing is safe: both calls run on the context's one stream and end synchronised, so the two
+    // are never live at once, and each call clears or rebuilds every word it reads before it reads it.
+    DBuf<int32_t> tlr_node, tlr_start, tlr_state, tlr_inv, tlr_cnt, tlr_first, tlr_fill, tlr_touched, tlr_flag, tlr_g;
+    DBuf<TlWin> tlr_win;
+    DBuf<unsigned long long> tlr_tot;
+    HBuf<int32_t> h_tlr_g;
+    HBuf<unsigned long long> h_tlr_tot;
+    double utl_ms = -1, htl_ms = -1;  // the *_ms diagnostics of the two calls
     // fit_advance_tl: the staged tails of the host entry point, the bad-input flag with its pinned
     // copy, and the *_ms diagnostic
     DBuf<int32_t> atl_tc, atl_tm, atl_tg, atl_g;
     HBuf<int32_t> h_atl;
     double atl_ms = -1;
-    // fit_hold_tl: the staged node lists, starts and states of the host entry point, node id ->
-    // position, per-position window count / range start / scatter cursor, the touched positions, the
-    // windows of the WHOLE call, the per-row refused flags, the counters of the check (fit_unplace_tl's
-    // layout) and of the grouping (touched, handed out), the two 64-bit totals, the pinned copies, and
-    // the *_ms diagnostic
-    DBuf<int32_t> htl_node, htl_start, htl_state, htl_inv, htl_cnt, htl_first, htl_fill, htl_touched, htl_flag, htl_g;
-    DBuf<HtlWin> htl_win;
-    DBuf<unsigned long long> htl_tot;
-    HBuf<int32_t> h_htl;
-    HBuf<unsigned long long> h_htl_tot;
-    double htl_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1499,13 +1493,66 @@ int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k
     return 0;
 }
 
+// --------------------------------------------------------------------------- the timeline writers
+// fit_place_tl_k, fit_unplace_tl, fit_advance_tl and fit_hold_tl follow one protocol, so that a bad
+// batch writes nothing and a failed write never leaves a half-written timeline in use:
+//   check phase  : ev[0], check() — launches that only read the timeline — ev[1], `flags` copied to
+//                  pinned memory, ONE synchronisation; verdict() then reads the flag words: a FIT_E_*
+//                  code with the call's own text fails the call, kTlNoWrite ends it with nothing to
+//                  write, 0 goes on.  No `flags`: no check phase at all (fit_advance_tl without tails).
+//   write phase  : ev[3], write(kept) — from its first launch on the run lists may be partly written
+//                  — ev[4], `result` copied to pinned memory, the closing synchronisation.  Any HIP
+//                  error in it drops the timeline (a watchdog trip of fit_place_tl does the same),
+//                  unless write() set `kept` to the code of a failure that wrote nothing.
+// *dev_ms: the device time of the two phases, summed.  Bounded launches on the context's stream,
+// nothing waits on another workgroup: no launch lock, no watchdog.
+struct TlBack {  // device words the host reads after a phase
+    void* host = nullptr;
+    const void* dev = nullptr;
+    size_t bytes = 0;
+};
+constexpr int kTlNoWrite = 1;  // verdict(): the call is done, no write phase
+
+template <class Check, class Verdict, class Write>
+int tl_write_impl(fit_ctx* c, const char* name, TlBack flags, Check check, Verdict verdict, TlBack result, Write write,
+                  double* dev_ms) {
+    hipStream_t st = c->st;
+    float ms = 0.f;
+    *dev_ms = 0;
+    if (flags.bytes) {
+        HIP_TRY(hipEventRecord(c->ev[0], st));
+        HIP_TRY(check());
+        HIP_TRY(hipEventRecord(c->ev[1], st));
+        HIP_TRY(hipMemcpyAsync(flags.host, flags.dev, flags.bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const int rc = verdict();
+        if (rc < 0) return rc;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        *dev_ms = ms;
+        if (rc == kTlNoWrite) return 0;
+    }
+    HIP_TRY(hipEventRecord(c->ev[3], st));
+    int kept = 0;
+    hipError_t e = write(kept);
+    if (e != hipSuccess && kept) return kept;
+    if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
+    if (e == hipSuccess && result.bytes)
+        e = hipMemcpyAsync(result.host, result.dev, result.bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
+    if (e != hipSuccess) {
+        c->have_tl = false;
+        return fail(FIT_E_HIP, "%s: %s; the timeline is dropped (fit_load_timeline)", name, hipGetErrorString(e));
+    }
+    *dev_ms += ms;
+    return 0;
+}
+
 // --------------------------------------------------------------------------- fit_place_tl_k
-// classify the batch, the jobs of each component in index order
-// (launch_joblists), ONE synchronisation that brings back the bad-input flag, the reject count and
-// the component offsets — so a bad batch fails before anything is reserved — then k_ptlk_commit per
-// chunk of PTLK_CHUNK jobs of every component's list, one workgroup per component.  Bounded
-// launches on the context's stream, nothing waits on another workgroup: no launch lock, no
-// watchdog.  Device pointers; out (J * kmax) and outs (J) are valid on return.
+// classify the batch and list the jobs of each component in index order
+// (launch_joblists); the flag words are the bad-input flag, the reject count and the component
+// offsets; then k_ptlk_commit per chunk of PTLK_CHUNK jobs of every component's list, one workgroup
+// per component.  Device pointers; out (J * kmax) and outs (J) are valid on return.
 int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32_t* out, int32_t* outs,
                     fit_stats* stats) {
     const double t0 = now_ms();
@@ -1521,51 +1568,47 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
         c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + ns) || c->h_jls.ensure(ns) ||
         c->ptlk_cnt.ensure(1) || c->h_ptlk.ensure(1))
         return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[0], st));
-    HIP_TRY(launch_ptlk_classify(st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, J, out, outs,
-                                 c->jcomp.p));
     int32_t* g = c->jls.p + joblists_scratch_ints(J);  // [0] rejected, [1] bad input, then jb and mb
     int32_t* jbd = g + 2;
-    HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
-    HIP_TRY(hipEventRecord(c->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(c->h_jls.p, g, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_jls.p[1]) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > kmax");
-    S.rejected = c->h_jls.p[0];
-    int32_t maxlen = 0;  // the longest component job list
-    for (int k = 0; k < C; ++k) maxlen = std::max(maxlen, c->h_jls.p[2 + k + 1] - c->h_jls.p[2 + k]);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    S.ms_device = ms;
-    if (maxlen > 0) {
-        int32_t chunk = PTLK_CHUNK;  // FIT_PTLK_CHUNK: tests put the launch seam inside a small batch
-        if (const char* e = getenv("FIT_PTLK_CHUNK")) chunk = std::max(1, std::min(atoi(e), PTLK_CHUNK));
-        const int threads = ptlk_threads(c->cls_maxn);
-        ExplainComps ec;
-        ec.ncomp = C;
-        for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
-        HIP_TRY(hipMemsetAsync(c->ptlk_cnt.p, 0, sizeof(int32_t), st));
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-        // from the first commit launch on the run lists may be partly reserved: an error drops the
-        // timeline, as a watchdog trip of fit_place_tl does
-        hipError_t e = hipSuccess;
-        int32_t done = 0;
-        for (; done < maxlen && e == hipSuccess; done += chunk)
-            e = launch_ptlk_commit(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd, done, chunk,
-                                   d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs, c->ptlk_cnt.p);
-        if (e != hipSuccess && done <= chunk) return fail(FIT_E_HIP, "k_ptlk_commit launch failed: %s", hipGetErrorString(e));
-        if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(c->h_ptlk.p, c->ptlk_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-        if (e != hipSuccess) {
-            c->have_tl = false;
-            return fail(FIT_E_HIP, "fit_place_tl_k: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
-        }
-        S.ms_device += ms;
-        S.placed = c->h_ptlk.p[0];
-    }
+    int32_t maxlen = 0;          // the longest component job list
+    int32_t chunk = PTLK_CHUNK;  // FIT_PTLK_CHUNK: tests put the launch seam inside a small batch
+    if (const char* e = getenv("FIT_PTLK_CHUNK")) chunk = std::max(1, std::min(atoi(e), PTLK_CHUNK));
+    const int rc = tl_write_impl(
+        c, "fit_place_tl_k", {c->h_jls.p, g, sizeof(int32_t) * ns},
+        [&] {
+            hipError_t e = launch_ptlk_classify(st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax,
+                                                J, out, outs, c->jcomp.p);
+            if (e == hipSuccess)
+                e = launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p);
+            return e;
+        },
+        [&]() -> int {
+            if (c->h_jls.p[1]) return fail(FIT_E_INVAL, "a job has a negative demand or nodes_k > kmax");
+            S.rejected = c->h_jls.p[0];
+            for (int k = 0; k < C; ++k) maxlen = std::max(maxlen, c->h_jls.p[2 + k + 1] - c->h_jls.p[2 + k]);
+            if (maxlen <= 0) return kTlNoWrite;
+            HIP_TRY(hipMemsetAsync(c->ptlk_cnt.p, 0, sizeof(int32_t), st));
+            return 0;
+        },
+        {c->h_ptlk.p, c->ptlk_cnt.p, sizeof(int32_t)},
+        [&](int& kept) {
+            const int threads = ptlk_threads(c->cls_maxn);
+            ExplainComps ec;
+            ec.ncomp = C;
+            for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+            hipError_t e = hipSuccess;
+            int32_t done = 0;
+            for (; done < maxlen && e == hipSuccess; done += chunk)
+                e = launch_ptlk_commit(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd, done,
+                                       chunk, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs,
+                                       c->ptlk_cnt.p);
+            if (e != hipSuccess && done <= chunk)  // the very first commit launch: nothing is reserved yet
+                kept = fail(FIT_E_HIP, "k_ptlk_commit launch failed: %s", hipGetErrorString(e));
+            return e;
+        },
+        &S.ms_device);
+    if (rc) return rc;
+    if (maxlen > 0) S.placed = c->h_ptlk.p[0];
     S.unplaced = J - S.placed - S.rejected;
     S.ms_total = now_ms() - t0;
     if (stats) *stats = S;
@@ -1573,162 +1616,148 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
 }
 
 // --------------------------------------------------------------------------- fit_unplace_tl
-// node id -> position, the check of the WHOLE batch, ONE synchronisation
-// that brings back the bad-input flag and the window count of every chunk — so a bad batch fails
-// before anything is written — then count, offsets, scatter and apply per chunk of UTL_CHUNK rows.
-// Bounded launches on the context's stream, nothing waits on another workgroup: no launch lock, no
-// watchdog.  Device pointers; *applied (host, may be null) is valid on return.
-int unplace_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
-                    const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
-                    int64_t* applied) {
-    const int H = c->tl_slots;
+// The rows fit_unplace_tl and fit_hold_tl take, on the device (nk: nullptr without a nodes_k column).
+struct TlRows {
+    const int32_t *cpu, *mem, *gpu, *wall;
+    const uint16_t* nk;
+    int32_t kmax;
+    const int32_t *node, *start;
+};
+
+// The check phase of both: node id -> position and the check of the WHOLE batch;
+// the flag words are the counters g (fit_device.h), nchunks window counts among them.
+int tl_rows_ensure(fit_ctx* c, int64_t nchunks) {
+    const size_t ng = 4 + (size_t)nchunks, np = std::max(c->nn, 1);
+    return c->tlr_inv.ensure(std::max(c->n, 1)) || c->tlr_cnt.ensure(np) || c->tlr_first.ensure(np) ||
+           c->tlr_fill.ensure(np) || c->tlr_g.ensure(ng) || c->h_tlr_g.ensure(ng);
+}
+TlBack tl_rows_flags(fit_ctx* c, int64_t nchunks) {
+    return {c->h_tlr_g.p, c->tlr_g.p, sizeof(int32_t) * (4 + (size_t)nchunks)};
+}
+hipError_t tl_rows_check(fit_ctx* c, int32_t J, const TlRows& r, int32_t chunk, int64_t nchunks) {
     hipStream_t st = c->st;
+    hipError_t e = hipMemsetAsync(c->tlr_g.p, 0, sizeof(int32_t) * (4 + (size_t)nchunks), st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->tlr_cnt.p, 0, sizeof(int32_t) * (size_t)std::max(c->nn, 1), st);
+    if (e == hipSuccess) e = launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->tlr_inv.p);
+    if (e == hipSuccess)
+        e = launch_utl_check(st, r.cpu, r.mem, r.gpu, r.nk, r.kmax, r.node, r.start, J, c->n, c->tl_slots, chunk,
+                             c->tlr_g.p);
+    return e;
+}
+// the flag, and the windows of the call's live rows
+int tl_rows_verdict(fit_ctx* c, int64_t nchunks, int64_t* total) {
+    if (c->h_tlr_g.p[2])
+        return fail(FIT_E_INVAL, "a live row has a negative demand, nodes_k > kmax, start >= %d slots, a node id "
+                                 "outside [0, %d) or the same node twice", c->tl_slots, c->n);
+    *total = 0;
+    for (int64_t k = 0; k < nchunks; ++k) *total += c->h_tlr_g.p[4 + k];
+    return 0;
+}
+
+// count, offsets, scatter and apply per chunk of UTL_CHUNK rows.  Device
+// pointers; *applied (host, may be null) is valid on return.
+int unplace_tl_impl(fit_ctx* c, int32_t J, const TlRows& r, int64_t* applied) {
     int32_t chunk = UTL_CHUNK;  // FIT_UTL_CHUNK: tests put the launch seam inside a small batch
     if (const char* e = getenv("FIT_UTL_CHUNK")) chunk = std::max(1, std::min(atoi(e), UTL_CHUNK));
     const int64_t nchunks = ((int64_t)J + chunk - 1) / chunk;
-    const size_t ng = 4 + (size_t)nchunks, np = std::max(c->nn, 1);
-    const size_t wcap = (size_t)std::min(J, chunk) * kmax;
-    if (c->utl_inv.ensure(std::max(c->n, 1)) || c->utl_cnt.ensure(np) || c->utl_first.ensure(np) ||
-        c->utl_fill.ensure(np) || c->utl_touched.ensure(std::min(wcap, np)) || c->utl_win.ensure(wcap) ||
-        c->utl_g.ensure(ng) || c->h_utl.ensure(ng))
+    const size_t wcap = (size_t)std::min(J, chunk) * r.kmax;
+    if (tl_rows_ensure(c, nchunks) || c->tlr_touched.ensure(std::min<size_t>(wcap, std::max(c->nn, 1))) ||
+        c->tlr_win.ensure(wcap))
         return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[0], st));
-    HIP_TRY(hipMemsetAsync(c->utl_g.p, 0, sizeof(int32_t) * ng, st));
-    HIP_TRY(hipMemsetAsync(c->utl_cnt.p, 0, sizeof(int32_t) * np, st));
-    HIP_TRY(launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->utl_inv.p));
-    HIP_TRY(launch_utl_check(st, cpu, mem, gpu, nk, kmax, node, start, J, c->n, H, chunk, c->utl_g.p));
-    HIP_TRY(hipEventRecord(c->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(c->h_utl.p, c->utl_g.p, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_utl.p[2])
-        return fail(FIT_E_INVAL, "a live row has a negative demand, nodes_k > kmax, start >= %d slots, a node id "
-                                 "outside [0, %d) or the same node twice", H, c->n);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    double dev_ms = ms;
     int64_t total = 0;
-    for (int64_t k = 0; k < nchunks; ++k) total += c->h_utl.p[4 + k];
-    if (total > 0 && c->nn > 0) {
-        HIP_TRY(hipEventRecord(c->ev[3], st));
-        // from the first apply launch on the run lists may be partly written: an error drops the
-        // timeline, as in fit_place_tl_k
-        hipError_t e = hipSuccess;
-        for (int64_t k = 0; k < nchunks && e == hipSuccess; ++k) {
-            const int32_t t0 = (int32_t)(k * chunk);
-            e = launch_utl_chunk(st, c->tlhdr.p, c->slab.p, c->nn, H, c->tl_slot_min, cpu, mem, gpu, wall, nk, kmax,
-                                 node, start, t0, std::min<int32_t>(J - t0, chunk), c->h_utl.p[4 + k], c->n,
-                                 c->utl_inv.p, c->utl_cnt.p, c->utl_first.p, c->utl_fill.p, c->utl_touched.p,
-                                 c->utl_win.p, c->utl_g.p);
-        }
-        if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-        if (e != hipSuccess) {
-            c->have_tl = false;
-            return fail(FIT_E_HIP, "fit_unplace_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
-        }
-        dev_ms += ms;
-    }
-    c->utl_ms = dev_ms;
+    double ms = 0;
+    const int rc = tl_write_impl(
+        c, "fit_unplace_tl", tl_rows_flags(c, nchunks), [&] { return tl_rows_check(c, J, r, chunk, nchunks); },
+        [&]() -> int {
+            const int v = tl_rows_verdict(c, nchunks, &total);
+            return v ? v : total > 0 && c->nn > 0 ? 0 : kTlNoWrite;
+        },
+        {},
+        [&](int&) {
+            hipError_t e = hipSuccess;
+            for (int64_t k = 0; k < nchunks && e == hipSuccess; ++k) {
+                const int32_t t0 = (int32_t)(k * chunk);
+                e = launch_utl_chunk(c->st, c->tlhdr.p, c->slab.p, c->nn, c->tl_slots, c->tl_slot_min, r.cpu, r.mem,
+                                     r.gpu, r.wall, r.nk, r.kmax, r.node, r.start, t0, std::min<int32_t>(J - t0, chunk),
+                                     c->h_tlr_g.p[4 + k], c->n, c->tlr_inv.p, c->tlr_cnt.p, c->tlr_first.p,
+                                     c->tlr_fill.p, c->tlr_touched.p, c->tlr_win.p, c->tlr_g.p);
+            }
+            return e;
+        },
+        &ms);
+    if (rc) return rc;
+    c->utl_ms = ms;
     if (applied) *applied = total;
     return 0;
 }
 
 // --------------------------------------------------------------------------- fit_advance_tl
-// with tails, their check and ONE synchronisation that brings the bad-input
-// flag back — so a bad tail fails before anything is written — then one launch, one wave per run
-// list.  Bounded launches on the context's stream, nothing waits on another workgroup:
-// no launch lock, no watchdog.  a >= 1; device pointers, n entries each, or all three null.
+// with tails, their check (the flag word: a tail below -1); then one launch,
+// one wave per run list.  a >= 1; device pointers, n entries each, or all three null.
 int advance_tl_impl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
-    const int H = c->tl_slots;
     hipStream_t st = c->st;
     if (c->atl_g.ensure(1) || c->h_atl.ensure(1)) return FIT_E_OOM;
-    float ms = 0.f;
-    double dev_ms = 0;
-    if (tc && c->n > 0) {
-        HIP_TRY(hipEventRecord(c->ev[0], st));
-        HIP_TRY(hipMemsetAsync(c->atl_g.p, 0, sizeof(int32_t), st));
-        HIP_TRY(launch_atl_check(st, tc, tm, tg, c->n, c->atl_g.p));
-        HIP_TRY(hipEventRecord(c->ev[1], st));
-        HIP_TRY(hipMemcpyAsync(c->h_atl.p, c->atl_g.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c->h_atl.p[0]) return fail(FIT_E_INVAL, "a tail value is below -1");
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        dev_ms = ms;
-    }
-    HIP_TRY(hipEventRecord(c->ev[3], st));
-    // from here on the run lists may be partly written: an error drops the timeline, as in fit_place_tl_k
-    hipError_t e = launch_atl_advance(st, c->tlhdr.p, c->slab.p, c->nn, c->n, H, std::min(a, H), tc, tm, tg);
-    if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-    if (e != hipSuccess) {
-        c->have_tl = false;
-        return fail(FIT_E_HIP, "fit_advance_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
-    }
-    c->atl_ms = dev_ms + ms;
+    double ms = 0;
+    const int rc = tl_write_impl(
+        c, "fit_advance_tl", tc && c->n > 0 ? TlBack{c->h_atl.p, c->atl_g.p, sizeof(int32_t)} : TlBack{},
+        [&] {
+            const hipError_t e = hipMemsetAsync(c->atl_g.p, 0, sizeof(int32_t), st);
+            return e == hipSuccess ? launch_atl_check(st, tc, tm, tg, c->n, c->atl_g.p) : e;
+        },
+        [&]() -> int { return c->h_atl.p[0] ? fail(FIT_E_INVAL, "a tail value is below -1") : 0; }, {},
+        [&](int&) {
+            return launch_atl_advance(st, c->tlhdr.p, c->slab.p, c->nn, c->n, c->tl_slots, std::min(a, c->tl_slots), tc,
+                                      tm, tg);
+        },
+        &ms);
+    if (rc) return rc;
+    c->atl_ms = ms;
     return 0;
 }
 
 // --------------------------------------------------------------------------- fit_hold_tl
-// node id -> position and fit_unplace_tl's check of the WHOLE batch, ONE
-// synchronisation that brings back the bad-input flag and the window count — so a bad batch fails
-// before anything, out_state included, is written — then the windows of the whole call grouped by
-// node, the judge pass, the apply pass and the states with the two counts.  Bounded launches on the
-// context's stream, nothing waits on another workgroup: no launch lock, no watchdog.  Device
-// pointers; *applied and *refused (host, may be null) are valid on return.
-int hold_tl_impl(fit_ctx* c, int32_t J, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
-                 const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
-                 int32_t* out_state, int64_t* applied, int64_t* refused) {
-    const int H = c->tl_slots;
+// fit_unplace_tl's rows and check phase — nothing, out_state included, is
+// written before the flag is seen — then the windows of the whole call grouped by node, the judge
+// pass, the apply pass and the states with the two counts.  Device pointers; *applied and *refused
+// (host, may be null) are valid on return.
+int hold_tl_impl(fit_ctx* c, int32_t J, const TlRows& r, int32_t* out_state, int64_t* applied, int64_t* refused) {
     hipStream_t st = c->st;
     const int64_t nchunks = ((int64_t)J + UTL_CHUNK - 1) / UTL_CHUNK;  // of the check's window counts only
-    const size_t ng = 4 + (size_t)nchunks, np = std::max(c->nn, 1);
-    if (c->htl_inv.ensure(std::max(c->n, 1)) || c->htl_cnt.ensure(np) || c->htl_first.ensure(np) ||
-        c->htl_fill.ensure(np) || c->htl_flag.ensure(J) || c->htl_g.ensure(ng) || c->h_htl.ensure(ng) ||
-        c->htl_tot.ensure(2) || c->h_htl_tot.ensure(2))
+    if (tl_rows_ensure(c, nchunks) || c->tlr_flag.ensure(J) || c->tlr_tot.ensure(2) || c->h_tlr_tot.ensure(2))
         return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[0], st));
-    HIP_TRY(hipMemsetAsync(c->htl_g.p, 0, sizeof(int32_t) * ng, st));
-    HIP_TRY(hipMemsetAsync(c->htl_cnt.p, 0, sizeof(int32_t) * np, st));
-    HIP_TRY(hipMemsetAsync(c->htl_flag.p, 0, sizeof(int32_t) * (size_t)J, st));
-    HIP_TRY(hipMemsetAsync(c->htl_tot.p, 0, sizeof(unsigned long long) * 2, st));
-    HIP_TRY(launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->htl_inv.p));
-    HIP_TRY(launch_utl_check(st, cpu, mem, gpu, nk, kmax, node, start, J, c->n, H, UTL_CHUNK, c->htl_g.p));
-    HIP_TRY(hipEventRecord(c->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(c->h_htl.p, c->htl_g.p, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c->h_htl.p[2])
-        return fail(FIT_E_INVAL, "a live row has a negative demand, nodes_k > kmax, start >= %d slots, a node id "
-                                 "outside [0, %d) or the same node twice", H, c->n);
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    double dev_ms = ms;
     int64_t total = 0;
-    for (int64_t k = 0; k < nchunks; ++k) total += c->h_htl.p[4 + k];
-    if (total > INT32_MAX) return fail(FIT_E_OOM, "%lld windows in one call", (long long)total);
-    if (c->htl_win.ensure((size_t)std::max<int64_t>(total, 1)) ||
-        c->htl_touched.ensure((size_t)std::max<int64_t>(std::min<int64_t>(total, c->nn), 1)))
-        return FIT_E_OOM;
-    HIP_TRY(hipEventRecord(c->ev[3], st));
-    // from the apply launch on the run lists may be partly written: an error drops the timeline, as
-    // in fit_place_tl_k
-    hipError_t e = launch_htl_hold(st, c->tlhdr.p, c->slab.p, c->nn, H, c->tl_slot_min, cpu, mem, gpu, wall, nk, kmax,
-                                   node, start, J, (int32_t)total, c->n, c->htl_inv.p, c->htl_cnt.p, c->htl_first.p,
-                                   c->htl_fill.p, c->htl_touched.p, c->htl_win.p, c->htl_flag.p, c->htl_g.p);
-    if (e == hipSuccess) e = launch_htl_final(st, nk, kmax, start, J, c->htl_flag.p, out_state, c->htl_tot.p);
-    if (e == hipSuccess) e = hipEventRecord(c->ev[4], st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(c->h_htl_tot.p, c->htl_tot.p, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[3], c->ev[4]);
-    if (e != hipSuccess) {
-        c->have_tl = false;
-        return fail(FIT_E_HIP, "fit_hold_tl: %s; the timeline is dropped (fit_load_timeline)", hipGetErrorString(e));
-    }
-    c->htl_ms = dev_ms + ms;
-    if (applied) *applied = (int64_t)c->h_htl_tot.p[0];
-    if (refused) *refused = (int64_t)c->h_htl_tot.p[1];
+    double ms = 0;
+    const int rc = tl_write_impl(
+        c, "fit_hold_tl", tl_rows_flags(c, nchunks),
+        [&] {
+            hipError_t e = hipMemsetAsync(c->tlr_flag.p, 0, sizeof(int32_t) * (size_t)J, st);
+            if (e == hipSuccess) e = hipMemsetAsync(c->tlr_tot.p, 0, sizeof(unsigned long long) * 2, st);
+            return e == hipSuccess ? tl_rows_check(c, J, r, UTL_CHUNK, nchunks) : e;
+        },
+        [&]() -> int {
+            const int v = tl_rows_verdict(c, nchunks, &total);
+            if (v) return v;
+            if (total > INT32_MAX) return fail(FIT_E_OOM, "%lld windows in one call", (long long)total);
+            if (c->tlr_win.ensure((size_t)std::max<int64_t>(total, 1)) ||
+                c->tlr_touched.ensure((size_t)std::max<int64_t>(std::min<int64_t>(total, c->nn), 1)))
+                return FIT_E_OOM;
+            return 0;
+        },
+        {c->h_tlr_tot.p, c->tlr_tot.p, sizeof(unsigned long long) * 2},
+        [&](int&) {
+            hipError_t e = launch_htl_hold(st, c->tlhdr.p, c->slab.p, c->nn, c->tl_slots, c->tl_slot_min, r.cpu, r.mem,
+                                           r.gpu, r.wall, r.nk, r.kmax, r.node, r.start, J, (int32_t)total, c->n,
+                                           c->tlr_inv.p, c->tlr_cnt.p, c->tlr_first.p, c->tlr_fill.p, c->tlr_touched.p,
+                                           c->tlr_win.p, c->tlr_flag.p, c->tlr_g.p);
+            if (e == hipSuccess)
+                e = launch_htl_final(st, r.nk, r.kmax, r.start, J, c->tlr_flag.p, out_state, c->tlr_tot.p);
+            return e;
+        },
+        &ms);
+    if (rc) return rc;
+    c->htl_ms = ms;
+    if (applied) *applied = (int64_t)c->h_tlr_tot.p[0];
+    if (refused) *refused = (int64_t)c->h_tlr_tot.p[1];
     return 0;
 }
 
@@ -2378,19 +2407,48 @@ int fit_place_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t
     return 0;
 }
 
-// fit_place_tl_k / fit_place_tl_k_device: fit_when_k's tests (a query name: a sharded context is
-// refused); nodes_k against kmax and the demands are the device's flag word
-static int check_place_tl_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
-    const int rc = check_job_args(c, j, arrays, "fit_place_tl_k", 1);
+// fit_place_tl_k, fit_unplace_tl, fit_hold_tl and their *_device forms: fit_when_k's tests (a query
+// name: a sharded context is refused), then kmax; nodes_k against kmax, the demands and the rows
+// themselves are the device's flag word
+static int check_tl_rows_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax,
+                              const char* name) {
+    const int rc = check_job_args(c, j, arrays, name, 1);
     if (rc) return rc;
     if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+// the *_ms diagnostic of a timeline writer: value < 0 until its first successful call
+static int tl_ms_get(fit_ctx* c, double fit_ctx::*value, const char* name, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->*value < 0) return fail(FIT_E_STATE, "no %s yet", name);
+    *ms = c->*value;
+    return 0;
+}
+
+// fit_unplace_tl, fit_hold_tl: the rows from host memory, one copy per column (j > 0)
+static int stage_rows(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                      const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
+                      TlRows& r) {
+    const size_t m = j, nn = (size_t)j * kmax, b = sizeof(int32_t) * m;
+    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) || (nk && c->jk.ensure(m)) ||
+        c->tlr_node.ensure(nn) || c->tlr_start.ensure(m))
+        return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
+    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, sizeof(uint16_t) * m, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->tlr_node.p, node, sizeof(int32_t) * nn, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->tlr_start.p, start, b, hipMemcpyHostToDevice, c->st));
+    r = {c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, nk ? c->jk.p : nullptr, kmax, c->tlr_node.p, c->tlr_start.p};
     return 0;
 }
 
 int fit_place_tl_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                    const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax, int32_t* out_node,
                    int32_t* out_start, fit_stats* stats) {
-    int rc = check_place_tl_k_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax);
+    int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax, "fit_place_tl_k");
     if (rc) return rc;
     if (j == 0) {
         if (stats) memset(stats, 0, sizeof *stats);
@@ -2413,7 +2471,7 @@ int fit_place_tl_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem
 int fit_place_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                           const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
                           int32_t* out_node, int32_t* out_start, fit_stats* stats) {
-    const int rc = check_place_tl_k_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax);
+    const int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax, "fit_place_tl_k");
     if (rc) return rc;
     if (j == 0) {
         if (stats) memset(stats, 0, sizeof *stats);
@@ -2423,74 +2481,41 @@ int fit_place_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32
     return place_tl_k_impl(c, j, {cpu, mem, gpu, wall, part, nk}, kmax, out_node, out_start, stats);
 }
 
-// fit_unplace_tl / fit_unplace_tl_device: fit_place_tl_k's tests (a query name: a sharded context
-// is refused); the rows themselves are the device's flag word
-static int check_unplace_tl_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
-    const int rc = check_job_args(c, j, arrays, "fit_unplace_tl", 1);
-    if (rc) return rc;
-    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
-    return 0;
-}
-
 int fit_unplace_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                    const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
                    int64_t* applied) {
-    int rc = check_unplace_tl_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax);
+    int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax, "fit_unplace_tl");
     if (rc) return rc;
     if (j == 0) {
         if (applied) *applied = 0;
         return 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t m = j, nn = (size_t)j * kmax;
-    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) || (nk && c->jk.ensure(m)) ||
-        c->utl_node.ensure(nn) || c->utl_start.ensure(m))
-        return FIT_E_OOM;
-    const size_t b = sizeof(int32_t) * m;
-    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
-    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, sizeof(uint16_t) * m, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->utl_node.p, node, sizeof(int32_t) * nn, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->utl_start.p, start, b, hipMemcpyHostToDevice, c->st));
-    return unplace_tl_impl(c, j, c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, nk ? c->jk.p : nullptr, kmax,
-                           c->utl_node.p, c->utl_start.p, applied);
+    TlRows r;
+    rc = stage_rows(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, r);
+    return rc ? rc : unplace_tl_impl(c, j, r, applied);
 }
 
 int fit_unplace_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                           const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node,
                           const int32_t* start, int64_t* applied) {
-    const int rc = check_unplace_tl_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax);
+    const int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, node, start}, kmax, "fit_unplace_tl");
     if (rc) return rc;
     if (j == 0) {
         if (applied) *applied = 0;
         return 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    return unplace_tl_impl(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, applied);
+    return unplace_tl_impl(c, j, {cpu, mem, gpu, wall, nk, kmax, node, start}, applied);
 }
 
-int fit_unplace_tl_ms(fit_ctx* c, double* ms) {
-    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
-    if (c->utl_ms < 0) return fail(FIT_E_STATE, "no fit_unplace_tl yet");
-    *ms = c->utl_ms;
-    return 0;
-}
+int fit_unplace_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::utl_ms, "fit_unplace_tl", ms); }
 
-// fit_hold_tl / fit_hold_tl_device: fit_unplace_tl's tests, out_state among the arrays; the rows
-// themselves are the device's flag word
-static int check_hold_tl_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
-    const int rc = check_job_args(c, j, arrays, "fit_hold_tl", 1);
-    if (rc) return rc;
-    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
-    return 0;
-}
-
+// fit_hold_tl: out_state among the arrays
 int fit_hold_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                 const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node, const int32_t* start,
                 int32_t* out_state, int64_t* applied, int64_t* refused) {
-    int rc = check_hold_tl_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax);
+    int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax, "fit_hold_tl");
     if (rc) return rc;
     if (j == 0) {
         if (applied) *applied = 0;
@@ -2498,22 +2523,13 @@ int fit_hold_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, c
         return 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t m = j, nn = (size_t)j * kmax;
-    if (c->jcpu.ensure(m) || c->jmem.ensure(m) || c->jgpu.ensure(m) || c->jwall.ensure(m) || (nk && c->jk.ensure(m)) ||
-        c->htl_node.ensure(nn) || c->htl_start.ensure(m) || c->htl_state.ensure(m))
-        return FIT_E_OOM;
-    const size_t b = sizeof(int32_t) * m;
-    HIP_TRY(hipMemcpyAsync(c->jcpu.p, cpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jmem.p, mem, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jgpu.p, gpu, b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->jwall.p, wall, b, hipMemcpyHostToDevice, c->st));
-    if (nk) HIP_TRY(hipMemcpyAsync(c->jk.p, nk, sizeof(uint16_t) * m, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->htl_node.p, node, sizeof(int32_t) * nn, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(hipMemcpyAsync(c->htl_start.p, start, b, hipMemcpyHostToDevice, c->st));
-    rc = hold_tl_impl(c, j, c->jcpu.p, c->jmem.p, c->jgpu.p, c->jwall.p, nk ? c->jk.p : nullptr, kmax, c->htl_node.p,
-                      c->htl_start.p, c->htl_state.p, applied, refused);
+    TlRows r;
+    rc = stage_rows(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, r);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_state, c->htl_state.p, b, hipMemcpyDeviceToHost, c->st));
+    if (c->tlr_state.ensure(j)) return FIT_E_OOM;
+    rc = hold_tl_impl(c, j, r, c->tlr_state.p, applied, refused);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_state, c->tlr_state.p, sizeof(int32_t) * (size_t)j, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
     return 0;
 }
@@ -2521,7 +2537,7 @@ int fit_hold_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, c
 int fit_hold_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                        const int32_t* wall, const uint16_t* nk, int32_t kmax, const int32_t* node,
                        const int32_t* start, int32_t* out_state, int64_t* applied, int64_t* refused) {
-    const int rc = check_hold_tl_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax);
+    const int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, node, start, out_state}, kmax, "fit_hold_tl");
     if (rc) return rc;
     if (j == 0) {
         if (applied) *applied = 0;
@@ -2529,15 +2545,10 @@ int fit_hold_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t*
         return 0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    return hold_tl_impl(c, j, cpu, mem, gpu, wall, nk, kmax, node, start, out_state, applied, refused);
+    return hold_tl_impl(c, j, {cpu, mem, gpu, wall, nk, kmax, node, start}, out_state, applied, refused);
 }
 
-int fit_hold_tl_ms(fit_ctx* c, double* ms) {
-    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
-    if (c->htl_ms < 0) return fail(FIT_E_STATE, "no fit_hold_tl yet");
-    *ms = c->htl_ms;
-    return 0;
-}
+int fit_hold_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::htl_ms, "fit_hold_tl", ms); }
 
 // fit_advance_tl / fit_advance_tl_device: the state tests of fit_unplace_tl, then a and the pointers
 static int check_advance_tl_args(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm, const int32_t* tg) {
@@ -2568,12 +2579,7 @@ int fit_advance_tl_device(fit_ctx* c, int32_t a, const int32_t* tc, const int32_
     return advance_tl_impl(c, a, tc, tm, tg);
 }
 
-int fit_advance_tl_ms(fit_ctx* c, double* ms) {
-    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
-    if (c->atl_ms < 0) return fail(FIT_E_STATE, "no fit_advance_tl yet");
-    *ms = c->atl_ms;
-    return 0;
-}
+int fit_advance_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::atl_ms, "fit_advance_tl", ms); }
 
 int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {
     if (!c) return fail(FIT_E_INVAL, "null ctx");

@@ -9,8 +9,8 @@
 //                 64 runs per step into registers: drop the runs that end at or before a, store the
 //                 survivors at `index - dropped` with `end - a`, merge or append the tail run
 //                 {H, tail}, take the exact column maxima on the way; the wave then waits for its
-//                 own list stores and re-reads the first TL_HEAD runs for the header, as k_utl_apply
-//                 does.  A sub-wave group of 8 lanes per short list, with one wave per longer list
+//                 own list stores and re-reads the first TL_HEAD runs for the header
+//                 (tl_refresh_head).  A sub-wave group of 8 lanes per short list, with one wave per longer list
 //                 in a second launch, was built and measured: it did not win.
 // The move is in place.  That is safe because (1) a lane's store needs its own load's data, and a
 // wave's load instruction has returned for all 64 lanes before the store instruction that uses it
@@ -27,7 +27,7 @@
 #include <algorithm>
 
 #include "fit_device.h"
-#include "fit_tl_reserve.h"
+#include "fit_tl_dense.h"
 
 namespace fitgpu {
 
@@ -86,10 +86,8 @@ __global__ __launch_bounds__(64) void k_atl_move(TlHdr* hdr, Seg* slab, int32_t 
             xm = max(xm, __shfl_xor(xm, off));
             xg = max(xg, __shfl_xor(xg, off));
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the list's writes before its re-read
-        if (lane < TL_HEAD) hp->head[lane] = lane < no ? sg[lane] : Seg{H, -1, -1, -1};
+        tl_refresh_head(hp, sg, no, H, lane);
         if (lane == 0) {
-            hp->cnt = no;
             hp->cpu = xc;  // exact: the only place a ceiling ever falls
             hp->mem = xm;
             hp->gpu = xg;

@@ -248,24 +248,41 @@ hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab
                               const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
                               int32_t* out_start, int32_t* placed);
 
-// ---- fit_unplace_tl (fit_unplace_tl.hip) -------------------------------
-// Rows go in chunks of at most UTL_CHUNK per launch sequence (count, offsets, scatter, apply), so a
-// launch is bounded whatever J is.  One window of one node, as k_utl_scatter groups them by node:
+// ---- the rows of fit_unplace_tl and fit_hold_tl, grouped by node (fit_unplace_tl.hip, DESIGN.md
+// §2h / §3.16) -----------------------------------------------------------------------------------
+// Both calls take the same rows (demands, wall, nodes_k, node list, start), check the WHOLE batch
+// with launch_utl_check, and group the windows of rows [t0, t0 + nj) by node with launch_utl_group:
+// fit_unplace_tl per chunk of at most UTL_CHUNK rows, so a launch sequence is bounded whatever J is;
+// fit_hold_tl once for the whole call (t0 = 0), since §2j judges per call.  The counter words g:
+//   g[0]          touched nodes so far (k_utl_count)         } zero before every launch_utl_group
+//   g[1]          windows handed out so far (k_utl_offsets)  }
+//   g[2]          the bad-input flag (k_utl_check)
+//   g[3]          pad
+//   g[4 + chunk]  windows of that chunk's live rows (k_utl_check; chunk = row / the check's `chunk`)
 constexpr int UTL_CHUNK = 16384;  // rows per launch sequence
-struct alignas(16) UtlWin {
+// One window of one node, 32 B: two 16-byte loads (fit_tl_dense.h runs them over the dense columns)
+struct alignas(16) TlWin {
     int32_t s, e;           // slots [s, e), clipped to the horizon
-    int32_t cpu, mem, gpu;  // the demand handed back
-    int32_t pad[3];
+    int32_t cpu, mem, gpu;  // the demand handed back (fit_unplace_tl) or reserved (fit_hold_tl)
+    int32_t row;            // its row: fit_hold_tl's windows set and obey the row's refused flag
+    int32_t pad[2];
 };
+static_assert(sizeof(TlWin) == 32, "one window is two 16-byte loads");
 hipError_t launch_utl_inverse(hipStream_t st, const TlHdr* hdr, int32_t nn, int32_t n, int32_t* inv);
 hipError_t launch_utl_check(hipStream_t st, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
                             const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t nj,
                             int32_t n, int32_t H, int32_t chunk, int32_t* g);
+// flag: null, or nj words: a row that names a node in no partition gets flag[row] = 1
+hipError_t launch_utl_group(hipStream_t st, int32_t nn, int32_t H, int32_t slot_min, const int32_t* jcpu,
+                            const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jk,
+                            int32_t kmax, const int32_t* node, const int32_t* start, int32_t t0, int32_t nj,
+                            int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
+                            int32_t* fill, int32_t* touched, TlWin* win, int32_t* flag, int32_t* g);
 hipError_t launch_utl_chunk(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t H, int32_t slot_min,
                             const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                             const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t t0,
                             int32_t nj, int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
-                            int32_t* fill, int32_t* touched, UtlWin* win, int32_t* g);
+                            int32_t* fill, int32_t* touched, TlWin* win, int32_t* g);
 
 // ---- fit_advance_tl (fit_advance_tl.hip) -------------------------------
 // Every node position's run list moved left by a slots, 1 <= a <= H, in place: one wave per list.
@@ -278,20 +295,12 @@ hipError_t launch_atl_advance(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn,
                               const int32_t* tc, const int32_t* tm, const int32_t* tg);
 
 // ---- fit_hold_tl (fit_hold_tl.hip) -------------------------------------
-// The rows, their check and the node id -> position table are fit_unplace_tl's (launch_utl_check,
-// launch_utl_inverse).  The windows of the WHOLE call are grouped by node, since §2j judges per
-// call: 32 B per window.  One window of one node, with the row it belongs to:
-struct alignas(16) HtlWin {
-    int32_t s, e;           // slots [s, e), clipped to the horizon
-    int32_t cpu, mem, gpu;  // the demand to reserve
-    int32_t row;            // the row whose refused flag the window sets and obeys
-    int32_t pad[2];
-};
+// The rows, their check, the node id -> position table and the grouping are the section above's.
 hipError_t launch_htl_hold(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t H, int32_t slot_min,
                            const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                            const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t nj,
                            int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
-                           int32_t* fill, int32_t* touched, HtlWin* win, int32_t* flag, int32_t* g);
+                           int32_t* fill, int32_t* touched, TlWin* win, int32_t* flag, int32_t* g);
 hipError_t launch_htl_final(hipStream_t st, const uint16_t* jk, int32_t kmax, const int32_t* start, int32_t nj,
                             const int32_t* flag, int32_t* out_state, unsigned long long* tot);
 

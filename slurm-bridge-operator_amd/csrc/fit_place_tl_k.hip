@@ -18,7 +18,7 @@
 //                     the start these are the answer; otherwise threads evaluate the one window
 //                     [start, start + d) on their nodes again.  `need` rounds of an LDS 64-bit
 //                     minimum take the workgroup's smallest; (reserve) one wave per pick reserves
-//                     with tl_reserve_any and refreshes the node's header.
+//                     with tl_reserve_any and refreshes the node's header (tl_refresh_head).
 // A component's rows are read and written by its workgroup alone, so nothing here waits for another
 // workgroup: no persistent grid, no launch lock, no watchdog.  Between jobs the waves of the
 // workgroup hand the run lists on through __syncthreads(), i.e. a workgroup-scope release before and
@@ -29,7 +29,7 @@
 #include <algorithm>
 
 #include "fit_device.h"
-#include "fit_tl_reserve.h"
+#include "fit_tl_dense.h"
 #include "fit_tl_walk.h"
 
 namespace fitgpu {
@@ -95,9 +95,8 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
     for (int t = lo; t < hi; ++t) {  // every branch on a job's values below is workgroup-uniform
         const int q = jl[t];
         const int32_t cpu = jcpu[q], mem = jmem[q], gpu = jgpu[q];
-        const int32_t need = min(max(jk ? (int32_t)jk[q] : 1, 1), min(kmax, FIT_KMAX));
-        const int64_t dw = ((int64_t)max(jwall[q], 0) + slot_min - 1) / slot_min;
-        const int32_t d = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));  // k_whenk_classify's `dur`
+        const int32_t need = tl_need(jk, q, kmax);
+        const int32_t d = tl_dur(jwall[q], slot_min);  // k_whenk_classify's `dur`
         const uint32_t pbit = 1u << (jpart[q] & 31);
         if (d > H) continue;  // no window inside the horizon: unplaced, nothing touched
         // the last job's readers of pick[] are behind its closing barrier; two barriers lie between
@@ -280,12 +279,8 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
                 Seg* sg = slab + (int64_t)pos * TL_MAX_SLOTS;
                 const int n = min(hp->cnt, TL_MAX_SLOTS);
                 const int nn = tl_reserve_any(sg, n, start, stop, cpu, mem, gpu, scr + (size_t)wave * (H + 2));
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the list's writes before its re-read
-                if (lane < TL_HEAD) hp->head[lane] = lane < nn ? sg[lane] : Seg{H, -1, -1, -1};
-                if (lane == 0) {
-                    hp->cnt = nn;
-                    out_node[(int64_t)q * kmax + r] = hp->orig;
-                }
+                tl_refresh_head(hp, sg, nn, H, lane);
+                if (lane == 0) out_node[(int64_t)q * kmax + r] = hp->orig;
             }
         if (tid == 0) {
             out_start[q] = start;
