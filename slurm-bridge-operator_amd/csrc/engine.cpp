@@ -1320,6 +1320,9 @@ static_assert(EX_FITS == FIT_WHY_FITS && EX_PARTITION == FIT_WHY_PARTITION && EX
                   EX_NO_NODES == FIT_WHY_NO_NODES && EX_RESOURCES == FIT_WHY_RESOURCES && FIT_KMAX == FIT_MAX_K,
               "fit_device.h and fitgpu.h disagree");
 static_assert(sizeof(fit_why) == 32, "fit_why is 32 bytes");
+// codes 1..4 of every family are LimitCode's by definition and pinned to fitgpu.h per family; 5 too:
+static_assert(FIT_ETA_NO_NODES == FIT_WHY_NO_NODES && FIT_ROOM_NO_NODES == FIT_WHY_NO_NODES,
+              "code 5 of FIT_ETA_* and FIT_ROOM_* is FIT_WHY_NO_NODES");
 // below this many jobs the caller's order is kept: the sort's three launches cost more than the
 // component passes a mixed wave adds
 constexpr int32_t kExplainSortJobs = 256;
@@ -1330,31 +1333,42 @@ struct JobCols {
     const uint16_t *part, *nk;
 };
 
-// The sequence fit_explain and fit_when share: the flag reset, classify() (rows' limit codes,
-// component per job, *bad), above kExplainSortJobs jobs of several components the jobs in
-// component order, then walk(components, job list, live count, job component ids).
+// The query frame's host side.  The component node offsets as a kernel argument:
+ExplainComps query_comps(const fit_ctx* c) {
+    ExplainComps ec;
+    ec.ncomp = c->ncomp;
+    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, c->ncomp)];
+    return ec;
+}
+// Above `threshold` jobs on several components, the classified jobs (c->jcomp) in component order
+// (launch_joblists): *jl the list and *live its length on the device, the jobs that have a
+// component; otherwise both nullptr, the caller's order.
+int query_joblist(fit_ctx* c, int32_t J, int32_t threshold, const int32_t** jl, const int32_t** live) {
+    const int C = c->ncomp;
+    *jl = *live = nullptr;
+    if (J <= threshold || C <= 1) return 0;
+    if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
+        c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
+        return FIT_E_OOM;
+    int32_t* g = c->jls.p + joblists_scratch_ints(J);
+    int32_t* jbd = g + 2;
+    HIP_TRY(launch_joblists(c->st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
+    *jl = c->jl.p;
+    *live = jbd + C;
+    return 0;
+}
+
+// The sequence fit_explain, fit_when and fit_room share: the flag reset, classify() (rows' limit
+// codes, component per job, *bad), above kExplainSortJobs jobs of several components the jobs in
+// component order, then walk(components, job list, live count).
 template <class Classify, class Walk>
 int query_impl(fit_ctx* c, int32_t J, int32_t* bad, Classify classify, Walk walk) {
-    const int C = c->ncomp;
-    hipStream_t st = c->st;
     if (c->jcomp.ensure(std::max(J, 1))) return FIT_E_OOM;
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), c->st));
     HIP_TRY(classify());
-    const int32_t *jl = nullptr, *live = nullptr;
-    if (J > kExplainSortJobs && C > 1) {
-        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
-            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
-            return FIT_E_OOM;
-        int32_t* g = c->jls.p + joblists_scratch_ints(J);
-        int32_t* jbd = g + 2;
-        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
-        jl = c->jl.p;
-        live = jbd + C;  // jobs that have a component
-    }
-    ExplainComps ec;
-    ec.ncomp = C;
-    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
-    HIP_TRY(walk(ec, jl, live));
+    const int32_t *jl, *live;
+    if (const int rc = query_joblist(c, J, kExplainSortJobs, &jl, &live)) return rc;
+    HIP_TRY(walk(query_comps(c), jl, live));
     return 0;
 }
 
@@ -1380,10 +1394,6 @@ static_assert(ETA_NOW == FIT_ETA_NOW && ETA_PARTITION == FIT_ETA_PARTITION && ET
                   ETA_LIMIT_CPUS == FIT_ETA_LIMIT_CPUS && ETA_LIMIT_MEM == FIT_ETA_LIMIT_MEM &&
                   ETA_NO_NODES == FIT_ETA_NO_NODES && ETA_LATER == FIT_ETA_LATER && ETA_HORIZON == FIT_ETA_HORIZON,
               "fit_device.h and fitgpu.h disagree");
-static_assert(FIT_ETA_PARTITION == FIT_WHY_PARTITION && FIT_ETA_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
-                  FIT_ETA_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && FIT_ETA_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
-                  FIT_ETA_NO_NODES == FIT_WHY_NO_NODES,
-              "FIT_ETA_1..5 are FIT_WHY_1..5");
 static_assert(sizeof(fit_eta) == 32, "fit_eta is 32 bytes");
 // nodes a wave walks at least before the node range is sliced further (explain_slices; fit_explain
 // keeps 32 rows): a node costs a header load and a dependent load per four runs, so a short batch
@@ -1414,10 +1424,6 @@ static_assert(ROOM_SOME == FIT_ROOM_SOME && ROOM_PARTITION == FIT_ROOM_PARTITION
                   ROOM_LIMIT_MEM == FIT_ROOM_LIMIT_MEM && ROOM_NO_NODES == FIT_ROOM_NO_NODES &&
                   ROOM_NONE == FIT_ROOM_NONE,
               "fit_device.h and fitgpu.h disagree");
-static_assert(FIT_ROOM_PARTITION == FIT_WHY_PARTITION && FIT_ROOM_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
-                  FIT_ROOM_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && FIT_ROOM_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
-                  FIT_ROOM_NO_NODES == FIT_WHY_NO_NODES,
-              "FIT_ROOM_1..5 are FIT_WHY_1..5");
 static_assert(sizeof(struct fit_room) == 40 && offsetof(struct fit_room, copies) == 16 &&
                   offsetof(struct fit_room, best_node) == 24,
               "fit_room is 40 bytes, copies at 16");
@@ -1471,21 +1477,10 @@ int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k
                                   c->tl_slot_min, out, out_node, c->jcomp.p, bad));
     if (C < 1) return 0;  // no node in any partition: every row is final
     // a count workgroup walks the nodes once for WHENK_GROUP jobs of one component: order the jobs
-    // by component when a group would mix them (query_impl's job list)
-    const int32_t *jl = nullptr, *live = nullptr;
-    if (J > WHENK_GROUP && C > 1) {
-        if (c->jl.ensure(J) || c->jpk.ensure(J + 1) ||
-            c->jls.ensure(std::max<size_t>(joblists_scratch_ints(J), 1) + 2 * (C + 1) + 2))
-            return FIT_E_OOM;
-        int32_t* g = c->jls.p + joblists_scratch_ints(J);
-        int32_t* jbd = g + 2;
-        HIP_TRY(launch_joblists(st, c->jcomp.p, J, C, c->jls.p, g, jbd, jbd + C + 1, c->jl.p, c->jpk.p));
-        jl = c->jl.p;
-        live = jbd + C;  // jobs that have a component
-    }
-    ExplainComps ec;
-    ec.ncomp = C;
-    for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+    // by component when a group would mix them
+    const int32_t *jl, *live;
+    if (const int rc = query_joblist(c, J, WHENK_GROUP, &jl, &live)) return rc;
+    const ExplainComps ec = query_comps(c);
     for (int32_t t0 = 0; t0 < J; t0 += WHENK_CHUNK)
         HIP_TRY(launch_whenk_chunk(st, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, d.cpu, d.mem, d.gpu, d.wall,
                                    d.part, t0, std::min<int32_t>(J - t0, WHENK_CHUNK), J, kmax, c->jcomp.p, jl, live, S,
@@ -1593,9 +1588,7 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
         {c->h_ptlk.p, c->ptlk_cnt.p, sizeof(int32_t)},
         [&](int& kept) {
             const int threads = ptlk_threads(c->cls_maxn);
-            ExplainComps ec;
-            ec.ncomp = C;
-            for (int k = 0; k <= 32; ++k) ec.nb[k] = c->nb[std::min(k, C)];
+            const ExplainComps ec = query_comps(c);
             hipError_t e = hipSuccess;
             int32_t done = 0;
             for (; done < maxlen && e == hipSuccess; done += chunk)

@@ -167,18 +167,23 @@ struct SmallBatch {
     uint16_t part[SMALL_ARGJ], nk[SMALL_ARGJ];
 };
 
+// ---- the job-side queries (fit_query.h, DESIGN.md §3.11 "The query frame") --------------------
+// What the partition-limit rule (job_limit) says of a job.  Codes 1..4 of every query's row are
+// these; engine.cpp pins each family to include/fitgpu.h.
+enum LimitCode : int32_t { LIM_NONE = 0, LIM_PARTITION = 1, LIM_LIMIT_TIME = 2, LIM_LIMIT_CPUS = 3, LIM_LIMIT_MEM = 4 };
+
 // ---- fit_explain (fit_explain.hip) ------------------------------------
 // The codes of include/fitgpu.h FIT_WHY_* (engine.cpp asserts they agree).
 enum ExplainCode : int32_t {
-    EX_FITS = 0,
-    EX_PARTITION = 1,
-    EX_LIMIT_TIME = 2,
-    EX_LIMIT_CPUS = 3,
-    EX_LIMIT_MEM = 4,
+    EX_FITS = LIM_NONE,
+    EX_PARTITION = LIM_PARTITION,
+    EX_LIMIT_TIME = LIM_LIMIT_TIME,
+    EX_LIMIT_CPUS = LIM_LIMIT_CPUS,
+    EX_LIMIT_MEM = LIM_LIMIT_MEM,
     EX_NO_NODES = 5,
     EX_RESOURCES = 6,
 };
-// Component node offsets in k_explain_count's kernel arguments: nb[c] .. nb[c + 1], c < ncomp.
+// Component node offsets in a query kernel's arguments: nb[c] .. nb[c + 1], c < ncomp.
 struct ExplainComps {
     int32_t nb[33];
     int32_t ncomp;
@@ -194,13 +199,13 @@ hipError_t launch_explain(hipStream_t st, const NodeRec* rec, const ExplainComps
 int explain_slices(int32_t nj, int32_t maxn, int cus, int min_rows = 32);
 
 // ---- fit_when (fit_when.hip) -------------------------------------------
-// The codes of include/fitgpu.h FIT_ETA_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
+// The codes of include/fitgpu.h FIT_ETA_* (engine.cpp asserts they agree); 5 is EX_NO_NODES.
 enum EtaCode : int32_t {
-    ETA_NOW = 0,
-    ETA_PARTITION = 1,
-    ETA_LIMIT_TIME = 2,
-    ETA_LIMIT_CPUS = 3,
-    ETA_LIMIT_MEM = 4,
+    ETA_NOW = LIM_NONE,
+    ETA_PARTITION = LIM_PARTITION,
+    ETA_LIMIT_TIME = LIM_LIMIT_TIME,
+    ETA_LIMIT_CPUS = LIM_LIMIT_CPUS,
+    ETA_LIMIT_MEM = LIM_LIMIT_MEM,
     ETA_NO_NODES = 5,
     ETA_LATER = 6,
     ETA_HORIZON = 7,
@@ -305,13 +310,13 @@ hipError_t launch_htl_final(hipStream_t st, const uint16_t* jk, int32_t kmax, co
                             const int32_t* flag, int32_t* out_state, unsigned long long* tot);
 
 // ---- fit_room (fit_room.hip) -------------------------------------------
-// The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 1-5 are EX_*'s.
+// The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 5 is EX_NO_NODES.
 enum RoomCode : int32_t {
-    ROOM_SOME = 0,
-    ROOM_PARTITION = 1,
-    ROOM_LIMIT_TIME = 2,
-    ROOM_LIMIT_CPUS = 3,
-    ROOM_LIMIT_MEM = 4,
+    ROOM_SOME = LIM_NONE,
+    ROOM_PARTITION = LIM_PARTITION,
+    ROOM_LIMIT_TIME = LIM_LIMIT_TIME,
+    ROOM_LIMIT_CPUS = LIM_LIMIT_CPUS,
+    ROOM_LIMIT_MEM = LIM_LIMIT_MEM,
     ROOM_NO_NODES = 5,
     ROOM_NONE = 6,
 };

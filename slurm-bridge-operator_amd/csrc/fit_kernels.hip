@@ -53,6 +53,7 @@ __global__ __launch_bounds__(64) void k_commit(
 // The verdict on job q: -3 invalid job (negative demand or nodes_k > kmax), -2 rejected by its
 // partition's limits, -1 partition without nodes, else its component | 0x40 for a multi-node
 // job.  *rej (the FIT_REJECTED rows) and *k (rows of the job) for the out[] init.
+// The admission path's own copy of the partition-limit rule; the queries' is fit_query.h job_limit.
 __device__ __forceinline__ int job_code(int q, const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem,
                                         const int32_t* __restrict__ jgpu, const int32_t* __restrict__ jwall,
                                         const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk,

@@ -4,7 +4,7 @@
 // DESIGN.md §2g, §3.15).  gfx950.
 //
 // Ordinary bounded launches on the context's stream:
-//   k_ptlk_classify : per job, the partition-limit rule (k_whenk_classify's), the reject result in
+//   k_ptlk_classify : per job, the partition-limit rule (fit_query.h job_limit), the reject result in
 //                     out_node / out_start, and the job's component in launch_joblists' coding
 //                     (-2 rejected, -3 bad input, -1 no member node)
 //   launch_joblists : the jobs of each component, in index order inside a component
@@ -48,12 +48,9 @@ __global__ __launch_bounds__(256) void k_ptlk_classify(
     const int p = jpart[q];
     const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
     const int32_t need = max(jk ? (int32_t)jk[q] : 1, 1);
-    bool rej = p >= np;
-    if (!rej) {
-        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
-        rej = (mt >= 0 && w > mt) || (mc >= 0 && c > mc) || (mm >= 0 && m > mm);
-    }
-    int comp = rej ? -2 : ptab[96 + p];  // -1: no node carries the partition's bit (unplaced)
+    const JobLimit lim = job_limit(p, np, ptab, c, m, w);
+    const bool rej = lim.code != LIM_NONE;
+    int comp = rej ? -2 : lim.comp;  // -1: no node carries the partition's bit (unplaced)
     if (c < 0 || m < 0 || g < 0 || w < 0 || need > kmax) comp = -3;  // the whole call fails (FIT_E_INVAL)
     for (int i = 0; i < kmax; ++i) out_node[(int64_t)q * kmax + i] = rej && i == 0 ? -2 : -1;
     out_start[q] = -1;

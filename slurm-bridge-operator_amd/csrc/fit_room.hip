@@ -3,7 +3,7 @@
 // sum, the roomiest node and the resource that binds on each (include/fitgpu.h fit_room; DESIGN.md
 // §2e, §3.13).  gfx950.
 //
-// fit_explain's three bounded launches and its count frame (fit_explain.hip):
+// fit_explain's three bounded launches, in the query frame (fit_query.h):
 //   k_room_classify : per job, the partition-limit code, zeroed counters, the job's component
 //   k_room_count    : every live job × every row of its component.  Lanes = jobs, rows wave-uniform
 //                     (scalar loads of a NodeRec, four per wait), grid.y = explain_slices(), the 8
@@ -25,12 +25,12 @@
 #include <cstddef>
 
 #include "fit_device.h"
+#include "fit_query.h"
 
 namespace fitgpu {
 
-constexpr int RM_WAVES = 8;  // waves per count workgroup
-constexpr int RM_JOBS = 64;  // jobs per count workgroup (lanes)
-constexpr int RM_N32 = 5;    // members, nodes, by_gpu, by_cpu, by_mem
+constexpr int RM_WAVES = QUERY_WAVES, RM_JOBS = QUERY_JOBS;
+constexpr int RM_N32 = 5;  // members, nodes, by_gpu, by_cpu, by_mem
 constexpr int32_t RM_UNBOUNDED = 0x7fffffff;
 
 // fit_room as the kernels see it (include/fitgpu.h).  Between k_room_count and k_room_final `best`
@@ -52,26 +52,18 @@ __global__ __launch_bounds__(256) void k_room_classify(
     if (q >= nj) return;
     const int p = jpart[q];
     const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
-    int code = ROOM_SOME, comp = -1;
-    if (p >= np) {
-        code = ROOM_PARTITION;
-    } else {
-        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
-        if (mt >= 0 && w > mt) code = ROOM_LIMIT_TIME;
-        else if (mc >= 0 && c > mc) code = ROOM_LIMIT_CPUS;
-        else if (mm >= 0 && m > mm) code = ROOM_LIMIT_MEM;
-        else comp = ptab[96 + p];  // -1: no node carries the partition's bit
-    }
+    const JobLimit lim = job_limit(p, np, ptab, c, m, w);
+    int comp = lim.comp;
     if (c < 0 || m < 0 || g < 0 || w < 0) {  // the whole call fails (FIT_E_INVAL)
         comp = -1;
         atomicOr(bad, 1);
     }
     RoomRow r;
-    r.code = code;
+    r.code = lim.code;
     r.members = r.nodes = r.best = 0;
     r.copies = 0;
     // a limit code's row is final here; the others count into zeros (the max word's low half too)
-    r.best_node = code != ROOM_SOME ? -1 : 0;
+    r.best_node = lim.code != LIM_NONE ? -1 : 0;
     r.by_gpu = r.by_cpu = r.by_mem = 0;
     out[q] = r;
     jcomp[q] = (int8_t)comp;
@@ -132,7 +124,7 @@ __device__ __forceinline__ void room_row(const NodeRec& r, uint32_t pbit, const 
     a.key = key > a.key ? key : a.key;
 }
 
-// grid (job tiles, node slices); jl / live as k_explain_count's.
+// grid (job tiles, node slices); jl / live: fit_query.h's job list.
 __global__ __launch_bounds__(RM_WAVES * 64) void k_room_count(
     const NodeRec* __restrict__ rec, ExplainComps C, const int32_t* __restrict__ jl, const int32_t* __restrict__ live,
     int32_t nj, const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
@@ -141,16 +133,13 @@ __global__ __launch_bounds__(RM_WAVES * 64) void k_room_count(
     __shared__ int32_t red[RM_WAVES][RM_N32][RM_JOBS];
     __shared__ uint64_t red64[RM_WAVES][2][RM_JOBS];  // copies, max word
     __shared__ int32_t qs[RM_JOBS];
-    const int nlive = jl ? min(*live, nj) : nj;
-    if ((int64_t)blockIdx.x * RM_JOBS >= nlive) return;  // block-uniform
+    const int nlive = query_live(jl, live, nj);
+    if (query_idle<RM_JOBS>(nlive)) return;  // block-uniform
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * RM_JOBS + lane;
-    int q = -1;
-    if (t < nlive) q = jl ? jl[t] : t;
-    if (q >= nj) q = -1;
-    const int comp = q >= 0 ? (int)jcomp[q] : -1;
-    const bool on = comp >= 0 && comp < C.ncomp;
+    const QueryLane j = query_lane<RM_JOBS>(nlive, jl, nj, jcomp, C);
+    const int q = j.q;
+    const bool on = j.on;
     const RoomDiv dc = room_div(on ? jcpu[q] : 0), dm = room_div(on ? jmem[q] : 0), dg = room_div(on ? jgpu[q] : 0);
     const int32_t wall = on ? jwall[q] : 0;
     const uint32_t pbit = on ? 1u << (jpart[q] & 31) : 0u;
@@ -160,28 +149,19 @@ __global__ __launch_bounds__(RM_WAVES * 64) void k_room_count(
     acc.copies = 0;
     acc.key = 0;
 
-    const int S = gridDim.y, s = blockIdx.y;
-    uint64_t rem = __ballot(on);
-    while (rem) {  // wave-uniform: one pass per distinct component among the lanes
-        const int first = __builtin_ctzll(rem);
-        const int c = __builtin_amdgcn_readlane(comp, first);
-        const bool mine = on && comp == c;
-        rem &= ~__ballot(mine);
-        const int nb = C.nb[c], ne = C.nb[c + 1];
-        const int per = (ne - nb + S - 1) / S;          // rows of this component per slice
-        const int a = min(ne, nb + s * per), b = min(ne, a + per);
-        const int sub = (per + RM_WAVES - 1) / RM_WAVES;  // rows per wave
-        const int n0 = min(b, a + wave * sub), n1 = min(b, n0 + sub);
-        const uint32_t pb = mine ? pbit : 0u;
-        int x = n0;
-        for (; x + 4 <= n1; x += 4) {  // four scalar row loads per wait, as k_scan
+    QueryWalk w = query_walk(on);
+    while (w.rem) {  // wave-uniform: one pass per distinct component
+        const QueryRange r = query_next<RM_WAVES>(w, C, j.comp, on, wave);
+        const uint32_t pb = r.mine ? pbit : 0u;
+        int x = r.n0;
+        for (; x + 4 <= r.n1; x += 4) {  // four scalar row loads per wait, as k_scan
             NodeRec r[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) r[u] = rec[x + u];
 #pragma unroll
             for (int u = 0; u < 4; ++u) room_row(r[u], pb, dc, dm, dg, wall, acc);
         }
-        for (; x < n1; ++x) room_row(rec[x], pb, dc, dm, dg, wall, acc);
+        for (; x < r.n1; ++x) room_row(rec[x], pb, dc, dm, dg, wall, acc);
     }
 
 #pragma unroll
@@ -233,32 +213,23 @@ __global__ __launch_bounds__(256) void k_room_final(RoomRow* __restrict__ out, i
     out[q] = r;
 }
 
-// The rows on stream st in two calls, so that the caller can order the jobs by component in
-// between (launch_joblists over jcomp): `out` (nj rows of 40 B, 8-byte aligned) and *bad (1: a job
-// has a negative demand) are valid when the stream has drained.
+// The rows on stream st in two calls, the caller ordering the jobs by component in between: `out` (nj
+// rows of 40 B, 8-byte aligned) and *bad (1: a negative demand) are valid when the stream has drained.
 hipError_t launch_room_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
                                 const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                                 int32_t nj, void* out, int8_t* jcomp, int32_t* bad) {
-    if (nj <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_room_classify, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jpart, nj,
-                       ptab, np, static_cast<RoomRow*>(out), jcomp, bad);
-    return hipGetLastError();
+    return launch_per_job(st, nj, k_room_classify, jcpu, jmem, jgpu, jwall, jpart, nj, ptab, np,
+                          static_cast<RoomRow*>(out), jcomp, bad);
 }
 
 // Count and finalise.  jl / live / slices as launch_explain's.
 hipError_t launch_room(hipStream_t st, const NodeRec* rec, const ExplainComps& C, const int32_t* jcpu,
                        const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                        int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* out) {
-    if (nj <= 0) return hipSuccess;
-    if (C.ncomp < 0 || C.ncomp > 32 || slices < 1 || slices > 65535) return hipErrorInvalidValue;
     RoomRow* o = static_cast<RoomRow*>(out);
-    if (C.ncomp > 0) {
-        const int tiles = (nj + RM_JOBS - 1) / RM_JOBS;
-        hipLaunchKernelGGL(k_room_count, dim3(tiles, slices), dim3(RM_WAVES * 64), 0, st, rec, C, jl, live, nj,
-                           jcpu, jmem, jgpu, jwall, jpart, jcomp, o);
-    }
-    hipLaunchKernelGGL(k_room_final, dim3((nj + 255) / 256), dim3(256), 0, st, o, nj);
-    return hipGetLastError();
+    const hipError_t e = launch_per_tile(st, nj, C.ncomp, slices, k_room_count, rec, C, jl, live, nj, jcpu, jmem, jgpu,
+                                         jwall, jpart, jcomp, o);
+    return e != hipSuccess ? e : launch_per_job(st, nj, k_room_final, o, nj);
 }
 
 }  // namespace fitgpu

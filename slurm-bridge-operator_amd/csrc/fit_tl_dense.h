@@ -16,22 +16,12 @@
 #include <hip/hip_runtime.h>
 
 #include "fit_device.h"
+#include "fit_query.h"  // tl_dur, tl_need: a row's slots and node count
 #include "fit_tl_reserve.h"
 
 namespace fitgpu {
 
 constexpr int32_t TL_OVER = INT32_MIN;  // ROOM columns: the room of a slot that cannot be used at all
-
-// d of §2g / §2h / §2j: max(1, ceil(wall / slot_min)), a negative wall counting as 0
-__device__ __forceinline__ int32_t tl_dur(int32_t wall, int32_t slot_min) {
-    const int64_t dw = ((int64_t)max(wall, 0) + slot_min - 1) / slot_min;
-    return (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));
-}
-
-// need of a row that its call's check passed (need <= kmax <= FIT_KMAX), clamped all the same
-__device__ __forceinline__ int32_t tl_need(const uint16_t* jk, int q, int32_t kmax) {
-    return min(max(jk ? (int32_t)jk[q] : 1, 1), min(kmax, FIT_KMAX));
-}
 
 // Expand: 64 runs per load, then run by run the wave fills the run's slots.  ROOM: the columns hold
 // the room of each slot, a value below 0 becoming TL_OVER.  The caller's __syncthreads() follows.

@@ -3,19 +3,18 @@
 // fit_when).  Read-only: the run lists are only loaded.  gfx950.
 //
 // Three ordinary bounded launches, whatever J and N are:
-//   k_when_classify : per job, the partition-limit code (k_explain_classify's rule), `dur`, the
-//                     row's accumulators (key KEY_INF, counters 0) and the job's component
-//   k_when_walk     : every live job × every node of its component.  Lanes = jobs (demand and
-//                     the TlWalk state in VGPRs), node positions wave-uniform: the 96-B TlHdr
+//   k_when_classify : per job, the partition-limit code (job_limit), `dur`, the row's
+//                     accumulators (key KEY_INF, counters 0) and the job's component
+//   k_when_walk     : every live job × every node of its component, in the query frame
+//                     (fit_query.h).  Lanes = jobs (demand and the TlWalk state in VGPRs),
+//                     node positions wave-uniform: the 96-B TlHdr
 //                     comes in with scalar loads and its TL_HEAD runs are stepped; a longer list
 //                     continues in the slab, four Seg per wait, until no lane is live.  The walk
 //                     is fit_tl_walk.h's with lim = H — no cut: `hosts` needs every node's
-//                     answer — and a lane leaves a node at its first completed window.  grid.x
-//                     tiles the jobs (64 per workgroup), grid.y splits every component's nodes
-//                     into slices; the 8 waves of a workgroup walk sub-slices and meet in LDS:
-//                     per (workgroup, job) one 64-bit atomicMin of the key and at most three
-//                     integer atomicAdd, zeros skipped.  Min and integer sums do not depend on
-//                     the order, so the rows are exact and reproducible.
+//                     answer — and a lane leaves a node at its first completed window.  The 8
+//                     waves of a workgroup meet in LDS: per (workgroup, job) one 64-bit atomicMin
+//                     of the key and at most three integer atomicAdd, zeros skipped.  Min and
+//                     integer sums do not depend on the order: exact and reproducible rows.
 //   k_when_final    : the minimum key → start, node (TlHdr::orig), wait_min and the code.
 // No cross-workgroup wait of any kind: no watchdog, no persistent-launch lock.
 #include <hip/hip_runtime.h>
@@ -23,13 +22,13 @@
 #include <cstddef>
 
 #include "fit_device.h"
+#include "fit_query.h"
 #include "fit_tl_walk.h"
 
 namespace fitgpu {
 
-constexpr int WH_WAVES = 8;  // waves per walk workgroup
-constexpr int WH_JOBS = 64;  // jobs per walk workgroup (lanes)
-constexpr int WH_NCNT = 3;   // members, hosts, now
+constexpr int WH_WAVES = QUERY_WAVES, WH_JOBS = QUERY_JOBS;
+constexpr int WH_NCNT = 3;  // members, hosts, now
 
 // fit_eta while the launches run: `key` lies over the row's start / node fields
 struct alignas(32) EtaAcc {
@@ -54,25 +53,15 @@ __global__ __launch_bounds__(256) void k_when_classify(
     if (q >= nj) return;
     const int p = jpart[q];
     const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
-    int code = ETA_NOW, comp = -1;
-    if (p >= np) {
-        code = ETA_PARTITION;
-    } else {
-        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
-        if (mt >= 0 && w > mt) code = ETA_LIMIT_TIME;
-        else if (mc >= 0 && c > mc) code = ETA_LIMIT_CPUS;
-        else if (mm >= 0 && m > mm) code = ETA_LIMIT_MEM;
-        else comp = ptab[96 + p];  // -1: no node carries the partition's bit
-    }
+    const JobLimit lim = job_limit(p, np, ptab, c, m, w);
+    int comp = lim.comp;
     if (c < 0 || m < 0 || g < 0 || w < 0) {  // the whole call fails (FIT_E_INVAL)
         comp = -1;
         atomicOr(bad, 1);
     }
-    // wall → slots occupied: ceil(wall / slot_min), at least 1 (scan_tile_tl's rule)
-    const int64_t dw = ((int64_t)max(w, 0) + slot_min - 1) / slot_min;
     EtaAcc r;
-    r.code = code;
-    r.dur = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));
+    r.code = lim.code;
+    r.dur = tl_dur(w, slot_min);
     r.key = KEY_INF;  // start = node = -1
     r.wait_min = -1;
 #pragma unroll
@@ -116,9 +105,7 @@ __device__ __forceinline__ void when_node(const TlHdr& h, int x, const Seg* __re
     n[2] += w.got & (w.kra == 0);
 }
 
-// grid (job tiles, node slices).  jl != nullptr: the jobs in component order (launch_joblists'
-// list, *live of them); jl == nullptr: jobs in the caller's order.  Either way a wave walks the
-// components its lanes name one after the other, each lane judging only its own.
+// grid (job tiles, node slices); jl / live: fit_query.h's job list.  Each lane judges only its own component.
 __global__ __launch_bounds__(WH_WAVES * 64) void k_when_walk(
     const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, ExplainComps C, int32_t H,
     const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t nj, const int32_t* __restrict__ jcpu,
@@ -127,16 +114,13 @@ __global__ __launch_bounds__(WH_WAVES * 64) void k_when_walk(
     __shared__ uint64_t rkey[WH_WAVES][WH_JOBS];
     __shared__ int32_t red[WH_WAVES][WH_NCNT][WH_JOBS];
     __shared__ int32_t qs[WH_JOBS];
-    const int nlive = jl ? min(*live, nj) : nj;
-    if ((int64_t)blockIdx.x * WH_JOBS >= nlive) return;  // block-uniform
+    const int nlive = query_live(jl, live, nj);
+    if (query_idle<WH_JOBS>(nlive)) return;  // block-uniform
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * WH_JOBS + lane;
-    int q = -1;
-    if (t < nlive) q = jl ? jl[t] : t;
-    if (q >= nj) q = -1;
-    const int comp = q >= 0 ? (int)jcomp[q] : -1;
-    const bool on = comp >= 0 && comp < C.ncomp;
+    const QueryLane j = query_lane<WH_JOBS>(nlive, jl, nj, jcomp, C);
+    const int q = j.q;
+    const bool on = j.on;
     const int32_t cpu = on ? jcpu[q] : 0, mem = on ? jmem[q] : 0, gpu = on ? jgpu[q] : 0;
     const int32_t d = on ? out[q].dur : 1;  // k_when_classify's, before any atomic touches the row
     const uint32_t pbit = on ? 1u << (jpart[q] & 31) : 0u;
@@ -145,20 +129,11 @@ __global__ __launch_bounds__(WH_WAVES * 64) void k_when_walk(
 #pragma unroll
     for (int i = 0; i < WH_NCNT; ++i) n[i] = 0;
 
-    const int S = gridDim.y, s = blockIdx.y;
-    uint64_t rem = __ballot(on);
-    while (rem) {  // wave-uniform: one pass per distinct component among the lanes
-        const int first = __builtin_ctzll(rem);
-        const int c = __builtin_amdgcn_readlane(comp, first);
-        const bool mine = on && comp == c;
-        rem &= ~__ballot(mine);
-        const int nb = C.nb[c], ne = C.nb[c + 1];
-        const int per = (ne - nb + S - 1) / S;            // nodes of this component per slice
-        const int a = min(ne, nb + s * per), b = min(ne, a + per);
-        const int sub = (per + WH_WAVES - 1) / WH_WAVES;  // nodes per wave
-        const int n0 = min(b, a + wave * sub), n1 = min(b, n0 + sub);
-        const uint32_t pb = mine ? pbit : 0u;
-        for (int x = n0; x < n1; ++x) when_node(hdr[x], x, slab, pb, cpu, mem, gpu, d, H, best, n);
+    QueryWalk w = query_walk(on);
+    while (w.rem) {  // wave-uniform: one pass per distinct component
+        const QueryRange r = query_next<WH_WAVES>(w, C, j.comp, on, wave);
+        const uint32_t pb = r.mine ? pbit : 0u;
+        for (int x = r.n0; x < r.n1; ++x) when_node(hdr[x], x, slab, pb, cpu, mem, gpu, d, H, best, n);
     }
 
     rkey[wave][lane] = best;
@@ -209,37 +184,27 @@ __global__ __launch_bounds__(256) void k_when_final(EtaAcc* __restrict__ acc, in
     *reinterpret_cast<EtaRow*>(acc + q) = r;
 }
 
-// The query on stream st in two calls, so that the caller can order the jobs by component in
-// between (launch_joblists over jcomp): `out` (nj rows of 32 B) and *bad (1: a job has a negative
-// demand) are valid when the stream has drained.
+// The query on stream st in two calls, the caller ordering the jobs by component in between: `out`
+// (nj rows of 32 B) and *bad (1: a job has a negative demand) are valid when the stream has drained.
 hipError_t launch_when_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
                                 const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                                 const uint16_t* jpart, int32_t nj, int32_t slot_min, void* out, int8_t* jcomp,
                                 int32_t* bad) {
-    if (nj <= 0) return hipSuccess;
-    if (slot_min < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_when_classify, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jpart, nj,
-                       ptab, np, slot_min, static_cast<EtaAcc*>(out), jcomp, bad);
-    return hipGetLastError();
+    if (nj > 0 && slot_min < 1) return hipErrorInvalidValue;
+    return launch_per_job(st, nj, k_when_classify, jcpu, jmem, jgpu, jwall, jpart, nj, ptab, np, slot_min,
+                          static_cast<EtaAcc*>(out), jcomp, bad);
 }
 
-// Walk and finalise.  jl / live: the component-ordered job list and its length on the device, or
-// nullptr for the caller's order.  slices: grid.y of the walk (explain_slices).
+// Walk and finalise.  jl / live / slices as launch_explain's.
 hipError_t launch_when(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
                        int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
                        const uint16_t* jpart, int32_t nj, const int8_t* jcomp, const int32_t* jl,
                        const int32_t* live, int slices, void* out) {
-    if (nj <= 0) return hipSuccess;
-    if (C.ncomp < 0 || C.ncomp > 32 || slices < 1 || slices > 65535 || H < 1 || H > TL_MAX_SLOTS || slot_min < 1)
-        return hipErrorInvalidValue;
+    if (nj > 0 && (H < 1 || H > TL_MAX_SLOTS || slot_min < 1)) return hipErrorInvalidValue;
     EtaAcc* o = static_cast<EtaAcc*>(out);
-    if (C.ncomp > 0) {
-        const int tiles = (nj + WH_JOBS - 1) / WH_JOBS;
-        hipLaunchKernelGGL(k_when_walk, dim3(tiles, slices), dim3(WH_WAVES * 64), 0, st, hdr, slab, C, H, jl, live, nj,
-                           jcpu, jmem, jgpu, jpart, jcomp, o);
-    }
-    hipLaunchKernelGGL(k_when_final, dim3((nj + 255) / 256), dim3(256), 0, st, o, nj, hdr, slot_min);
-    return hipGetLastError();
+    const hipError_t e = launch_per_tile(st, nj, C.ncomp, slices, k_when_walk, hdr, slab, C, H, jl, live, nj, jcpu,
+                                         jmem, jgpu, jpart, jcomp, o);
+    return e != hipSuccess ? e : launch_per_job(st, nj, k_when_final, o, nj, hdr, slot_min);
 }
 
 }  // namespace fitgpu

@@ -5,8 +5,8 @@
 //
 // Ordinary bounded launches, whatever J and N are; the middle four run per chunk of jobs so that
 // the scratch stays bounded:
-//   k_whenk_classify : per job, the partition-limit code (k_when_classify's rule), `dur`, `need`,
-//                      the row's counters zeroed and the job's component
+//   k_whenk_classify : per job, the partition-limit code (job_limit), `dur`, `need`, the row's
+//                      counters zeroed and the job's component
 //   k_whenk_count    : one workgroup per (group of 8 jobs, node slice), threads = nodes.  A thread
 //                      loads its node's WHOLE run list once and steps the group's jobs over it:
 //                      for every maximal feasible stretch [a, b) of at least d slots of a job, +1
@@ -32,6 +32,7 @@
 #include <cstddef>
 
 #include "fit_device.h"
+#include "fit_query.h"
 #include "fit_tl_walk.h"
 
 namespace fitgpu {
@@ -58,51 +59,21 @@ __global__ __launch_bounds__(256) void k_whenk_classify(
     const int p = jpart[q];
     const int32_t c = jcpu[q], m = jmem[q], g = jgpu[q], w = jwall[q];
     const int32_t need = max(jk ? (int32_t)jk[q] : 1, 1);
-    int code = ETA_NOW, comp = -1;
-    if (p >= np) {
-        code = ETA_PARTITION;
-    } else {
-        const int mt = ptab[p], mc = ptab[32 + p], mm = ptab[64 + p];
-        if (mt >= 0 && w > mt) code = ETA_LIMIT_TIME;
-        else if (mc >= 0 && c > mc) code = ETA_LIMIT_CPUS;
-        else if (mm >= 0 && m > mm) code = ETA_LIMIT_MEM;
-        else comp = ptab[96 + p];  // -1: no node carries the partition's bit
-    }
+    const JobLimit lim = job_limit(p, np, ptab, c, m, w);
+    int comp = lim.comp;
     if (c < 0 || m < 0 || g < 0 || w < 0 || need > kmax) {  // the whole call fails (FIT_E_INVAL)
         comp = -1;
         atomicOr(bad, 1);
     }
-    // wall -> slots occupied: ceil(wall / slot_min), at least 1 (k_when_classify's rule)
-    const int64_t dw = ((int64_t)max(w, 0) + slot_min - 1) / slot_min;
     EtaKRow r;
     // a job without a component has no member node and is in no job list: its row is final here
-    r.code = code == ETA_NOW && comp < 0 ? ETA_NO_NODES : code;
-    r.dur = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));
+    r.code = lim.code == LIM_NONE && comp < 0 ? ETA_NO_NODES : lim.code;
+    r.dur = tl_dur(w, slot_min);
     r.need = need;
     r.start = r.wait_min = -1;
     r.members = r.hosts = r.now = r.ready = r.reserved = 0;
     out[q] = r;
     jcomp[q] = (int8_t)comp;
-}
-
-// The node slice [a, b) of component `comp` for slice blockIdx.y; false: nothing to do.
-__device__ __forceinline__ bool whenk_slice(const ExplainComps& C, int comp, int& a, int& b) {
-    if (comp < 0 || comp >= C.ncomp) return false;
-    const int nb = C.nb[comp], ne = C.nb[comp + 1];
-    const int per = (ne - nb + (int)gridDim.y - 1) / (int)gridDim.y;
-    a = min(ne, nb + (int)blockIdx.y * per);
-    b = min(ne, a + per);
-    return a < b;
-}
-
-// Position t of the batch -> job: the component-ordered list's (jl, *live of them) or the caller's
-// order; -1 behind the end.
-__device__ __forceinline__ int whenk_job(int t, const int32_t* __restrict__ jl, const int32_t* __restrict__ live,
-                                         int32_t njobs) {
-    const int nlive = jl ? min(*live, njobs) : njobs;
-    if (t >= nlive) return -1;
-    const int q = jl ? jl[t] : t;
-    return q >= 0 && q < njobs ? q : -1;
 }
 
 // grid (groups of WK_GROUP positions of the chunk [t0, t0 + nj), node slices); diff: the chunk's
@@ -125,7 +96,7 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
     uint32_t valid = 0;
 #pragma unroll
     for (int g = 0; g < WK_GROUP; ++g) {
-        const int qq = tb + g < nj ? whenk_job(t0 + tb + g, jl, live, njobs) : -1;
+        const int qq = tb + g < nj ? query_job(t0 + tb + g, jl, live, njobs) : -1;
         int c = qq >= 0 ? (int)jcomp[qq] : -1;
         if (c >= C.ncomp) c = -1;
         const bool on = c >= 0;
@@ -134,8 +105,7 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
         cpu[g] = on ? jcpu[qq] : 0;
         mem[g] = on ? jmem[qq] : 0;
         gpu[g] = on ? jgpu[qq] : 0;
-        const int64_t dw = on ? ((int64_t)max(jwall[qq], 0) + slot_min - 1) / slot_min : 1;
-        d[g] = (int32_t)max<int64_t>(1, min<int64_t>(dw, 0x7fffffff));  // k_whenk_classify's `dur`
+        d[g] = on ? tl_dur(jwall[qq], slot_min) : 1;  // k_whenk_classify's `dur`
         pbit[g] = on ? 1u << (jpart[qq] & 31) : 0u;
         valid |= on ? 1u << g : 0u;
     }
@@ -158,7 +128,7 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
         for (int g = 0; g < WK_GROUP; ++g) act |= ((valid >> g) & 1u) && comp[g] == c ? 1u << g : 0u;
         rem &= ~act;
         int a, b;
-        if (!whenk_slice(C, c, a, b)) continue;
+        if (!query_slice(C, c, a, b)) continue;
         for (int x = a + threadIdx.x; x < b; x += WK_THREADS) {
             const TlHdr h = hdr[x];
             // members; the header's column ceilings and d <= H reject a node without a walk (when_node's rule)
@@ -239,7 +209,7 @@ __global__ __launch_bounds__(256) void k_whenk_pick(const int32_t* __restrict__ 
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + wave;
     if (t >= nj) return;  // wave-uniform
-    const int q = whenk_job(t0 + t, jl, live, njobs);
+    const int q = query_job(t0 + t, jl, live, njobs);
     if (q < 0 || jcomp[q] < 0) return;  // rejected, or no member at all: start stays -1
     const int32_t need = out[q].need, d = out[q].dur;
     if (d > H) return;
@@ -280,11 +250,11 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_nodes(
     const uint16_t* __restrict__ jpart, const int8_t* __restrict__ jcomp, const EtaKRow* __restrict__ out,
     unsigned long long* __restrict__ top) {
     __shared__ unsigned long long best;
-    const int q = whenk_job(t0 + blockIdx.x, jl, live, njobs);
+    const int q = query_job(t0 + blockIdx.x, jl, live, njobs);
     if (q < 0) return;  // block-uniform
     const int32_t start = out[q].start;
     int a, b;
-    if (start < 0 || !whenk_slice(C, jcomp[q], a, b)) return;  // block-uniform
+    if (start < 0 || !query_slice(C, jcomp[q], a, b)) return;  // block-uniform
     const int32_t cpu = jcpu[q], mem = jmem[q], gpu = jgpu[q];
     const int32_t d = out[q].dur, need = min(out[q].need, WHENK_KEYS);
     const int32_t stop = start + d;  // <= H: k_whenk_pick found the start among s + d <= H
@@ -361,7 +331,7 @@ __global__ __launch_bounds__(256) void k_whenk_final(EtaKRow* __restrict__ out, 
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + wave;
     if (t >= nj) return;  // wave-uniform, as every return below
-    const int q = whenk_job(t0 + t, jl, live, njobs);
+    const int q = query_job(t0 + t, jl, live, njobs);
     if (q < 0) return;
     EtaKRow r = out[q];
     if (r.code != ETA_NOW) return;  // limit codes and jobs without a component: final since k_whenk_classify
@@ -402,9 +372,8 @@ hipError_t launch_whenk_classify(hipStream_t st, const int32_t* ptab, int32_t np
     if (slot_min < 1 || kmax < 1 || kmax > FIT_KMAX) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(out_node, 0xff, sizeof(int32_t) * (size_t)nj * kmax, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_whenk_classify, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jpart, jk,
-                       kmax, nj, ptab, np, slot_min, static_cast<EtaKRow*>(out), jcomp, bad);
-    return hipGetLastError();
+    return launch_per_job(st, nj, k_whenk_classify, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, nj, ptab, np, slot_min,
+                          static_cast<EtaKRow*>(out), jcomp, bad);
 }
 
 // ... then, per chunk of at most WHENK_CHUNK positions [t0, t0 + nj) of the batch: count, pick, nodes,

@@ -144,6 +144,19 @@ def test_exact_rows_hand_tables(engine, n):
         assert stats["bind_ties"] > 0 and stats["node_ties"] > 0, stats
 
 
+@pytest.mark.parametrize("j", [64, 256])
+def test_exact_rows_mixed_components_in_caller_order(engine, j):
+    """c3: 16 disjoint partitions, 16 components; up to 256 jobs keep the caller's order, so the
+    lanes of one wave name many components and the wave walks them one after the other."""
+    nodes, jobs, parts = synth.make_config("c3", 1000, j)
+    assert len(np.unique(nodes.part_mask)) == 16 and len(np.unique(jobs.part[:64])) >= 8
+    want = ref_room(nodes.cpu_free, nodes.mem_free, nodes.gpu_free, nodes.avail_min, nodes.part_mask, parts, jobs)
+    assert len(np.unique(want["members"][want["members"] > 0])) >= 8  # not vacuous: the components differ in size
+    engine.load_nodes(nodes)
+    engine.load_partitions(parts)
+    assert_rows(room_both(engine, jobs), want)
+
+
 # ---- 2. quotient edges and the 64-bit sum -------------------------------------------------------
 ONE_PART = synth.Partitions(np.full(1, -1, np.int32), np.full(1, -1, np.int32), np.full(1, -1, np.int32))
 EDGE_D = [1, 2, 3, 7, 2**30, 2**30 + 1, 2**31 - 1]

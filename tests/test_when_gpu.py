@@ -229,6 +229,30 @@ def test_exact_rows_awkward_shapes(engine, n, j, H):
         assert set(np.unique(got["code"]).tolist()) == set(range(8)), np.unique(got["code"])
 
 
+@pytest.mark.parametrize("j", [64, 256])
+def test_exact_rows_mixed_components_in_caller_order(engine, j):
+    """c3: 16 disjoint partitions, 16 components; up to 256 jobs keep the caller's order, so the
+    lanes of one wave name many components and the wave walks them one after the other.  H = 64,
+    up to five releases per node."""
+    H, slot_min = 64, 30
+    nodes, jobs, parts = synth.make_config("c3", 1000, j)
+    assert len(np.unique(nodes.part_mask)) == 16 and len(np.unique(jobs.part[:64])) >= 8
+    r = np.random.default_rng(64 + j)
+    k = r.integers(0, 6, nodes.n)
+    off = np.concatenate([[0], np.cumsum(k)]).astype(np.int32)
+    slot = np.concatenate([np.sort(r.choice(np.arange(1, H), m, replace=False)) for m in k]).astype(np.int32)
+    m = len(slot)
+    tline = synth.Timeline(slots=H, slot_min=slot_min, off=off, slot=slot, cpu=r.integers(1, 9, m).astype(np.int32),
+                           mem=(r.integers(0, 5, m) * 4096).astype(np.int32), gpu=r.integers(0, 2, m).astype(np.int32))
+    dense = po.ref_build_timeline(nodes, tline)
+    want = ref_when(dense, nodes.part_mask, parts, jobs, slot_min)
+    assert len(np.unique(want["members"][want["members"] > 0])) >= 8  # not vacuous: the components differ in size
+    engine.load_nodes(nodes)
+    engine.load_partitions(parts)
+    engine.load_timeline(tline)
+    assert_rows(when_both(engine, jobs), want)
+
+
 def test_largest_slot_min(engine):
     """The widest slot that still leaves 1,024 usable slots below avail_min = INT32_MAX: wait_min
     and dur near the top of int32 (wall + slot_min - 1 does not fit 32 bits).  start * slot_min
