@@ -247,7 +247,11 @@ struct MwTiles {
 // global address-space views of the helper's buffers: a plain (generic) pointer in a non-inlined
 // function compiles to flat loads, which also count in lgkmcnt — every LDS wait would then drain
 // the prefetched job stream
+#ifdef __HIP_DEVICE_COMPILE__
 #define GAS __attribute__((address_space(1)))
+#else  // (the host pass only parses device code)
+#define GAS
+#endif
 template <class T>
 __device__ __forceinline__ const GAS T* gview(const T* p) {
     return (const GAS T*)p;
@@ -332,6 +336,15 @@ __device__ __forceinline__ T* lds_opaque(T* p) {
 template <class T>
 __device__ __forceinline__ uint32_t mw_lds_addr(T* p) {
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p;
+}
+
+// lds_opaque for an LDS address that depends on runtime values: made uniform first, so that it
+// can live in an SGPR
+template <class T>
+__device__ __forceinline__ T* tm_lds(T* p) {
+    typedef __attribute__((address_space(3))) T* Lds;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)mw_lds_addr(p));  // uniform
+    return lds_opaque((T*)(Lds)(uintptr_t)a);
 }
 
 // The plan copied into SGPRs: an out-of-line function receives it through a generic pointer, and
@@ -465,10 +478,22 @@ __device__ __forceinline__ int32_t writelane_c(int32_t x, int32_t old) {  // com
 }
 __device__ __forceinline__ int32_t readlane(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
-// Wait until job tt's scan tile is complete (uniform; `ready` = tiles known complete, they finish
-// roughly in order).  false: the decider halted / a watchdog tripped.
+// One CommitResult through the shared block's res[4]: one lane puts it, every wave gets it after
+// the next barrier.
+__device__ __forceinline__ void put_result(int32_t* res, const CommitResult& r) {
+    res[0] = r.done;
+    res[1] = r.stop;
+    res[2] = r.dirty;
+    res[3] = r.placed;
+}
+__device__ __forceinline__ CommitResult get_result(const int32_t* res) {
+    return CommitResult{res[0], res[1], res[2], res[3]};
+}
+
 // Publish the window's job tiles [pubt, upto) (uniform; lane 0 claims the range by an LDS CAS).
-__device__ __noinline__ void mw_publish(const MwTiles& T, MwShared* S, unsigned upto) {
+// Sh: the commit's shared block (MwShared, TmShared).
+template <class Sh>
+__device__ __noinline__ void commit_publish(const MwTiles& T, Sh* S, unsigned upto) {
     const int lane = threadIdx.x & 63;
     unsigned from = upto;  // nothing claimed
     if (lane == 0) {
@@ -484,17 +509,20 @@ __device__ __noinline__ void mw_publish(const MwTiles& T, MwShared* S, unsigned 
     from = (unsigned)__builtin_amdgcn_readlane((int)from, 0);
     if (from >= upto) return;
     // claimed [from, upto): what the tasks' scans read — the round's plan, bounds, tile counters
-    // (written through) and node rows (written through, or released) — was stored and drained by
-    // the committer wave before the block barrier this wave has passed: no fence here (R1)
+    // (written through) and the last commit's write-backs (written through, or released) — was
+    // stored and drained by the committer wave before the block barrier this wave has passed: no
+    // fence here (R1)
     engine_publish(T.ctl, T.ring, from, upto, T.need, T.round, T.comp);
 }
 
+// Wait until job tt's scan tile is complete (uniform; `ready` = tiles known complete, they finish
+// roughly in order).  false: the decider halted / a watchdog tripped.
 __device__ __forceinline__ bool mw_tile_ready(const MwTiles& T, int tt, int& ready, MwShared* S) {
     if (!T.tdone) return true;
     const int tile = __builtin_amdgcn_readfirstlane(tt) / SCAN_JOBS;
     if (tile < ready) return true;
     if (T.ring && (unsigned)tile + ENGINE_AHEAD > lds_ld(&S->pubt))
-        mw_publish(T, S, min((unsigned)tile + ENGINE_AHEAD, T.ntj));
+        commit_publish(T, S, min((unsigned)tile + ENGINE_AHEAD, T.ntj));
     for (unsigned sp = 0;; ++sp) {
         if (__hip_atomic_load(gview(T.tdone) + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >=
             T.need)
@@ -1329,19 +1357,14 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
         // block-uniform: the 64-row set with recycling, or UCAP rows
         const CommitResult r = S->ucap == (uint32_t)MW_UCAP ? mw_decider<true>(P, S, out, kmax)
                                                             : mw_decider<false>(P, S, out, kmax);
-        if (threadIdx.x == 0) {
-            S->res[0] = r.done;
-            S->res[1] = r.stop;
-            S->res[2] = r.dirty;
-            S->res[3] = r.placed;
-        }
+        if (threadIdx.x == 0) put_result(S->res, r);
     } else {
         // waves 1.. : helpers 1..MW_H, with one or two dirty rows per lane (block-uniform)
         if (S->ucap == (uint32_t)MW_UCAP) mw_helper<1>(P, S, rec, cand, bnd, wjob, wave, T);
         else mw_helper<2>(P, S, rec, cand, bnd, wjob, wave, T);
     }
     __syncthreads();
-    const CommitResult r{S->res[0], S->res[1], S->res[2], S->res[3]};
+    const CommitResult r = get_result(S->res);
     // write the dirty rows back for the next round's scan, through (sc1: the next round's
     // publish needs no release fence for them; {cpu, mem} as one 8-B word, then gpu)
     for (int u = threadIdx.x; u < r.dirty; u += MW_WAVES * 64) {

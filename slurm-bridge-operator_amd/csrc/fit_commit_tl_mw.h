@@ -109,42 +109,11 @@ __device__ __forceinline__ void wait_clock_end(uint32_t* wclk, unsigned spins) {
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// lds_opaque for an LDS address that depends on runtime values (region / prefix-minimum bases
-// follow R): made uniform first, so it can live in an SGPR
-template <class T>
-__device__ __forceinline__ T* tm_lds(T* p) {
-    uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p);
-    asm volatile("" : "+s"(a));
-    return (T*)(__attribute__((address_space(3))) T*)(uintptr_t)a;
-}
-
 #ifndef TL_AHEAD
 #define TL_AHEAD 2  // job tiles published ahead of the helper that needs them (0: all up front).
                     // C5 k_engine_tl: 1 / 2 / 4 / 8 -> 174.7 / 129.9 / 133.8 / 140.5 ms (r03d/e):
                     // tiles past a round's stop are scanned for nothing, too few starve the helpers
 #endif
-
-// Publish the window's job tiles [pubt, upto) (uniform; lane 0 claims the range by an LDS CAS) —
-// fit_commit_mw.h mw_publish for this layout.
-__device__ __noinline__ void tm_publish(const MwTiles& T, TmShared* S, unsigned upto) {
-    const int lane = threadIdx.x & 63;
-    unsigned from = upto;
-    if (lane == 0) {
-        unsigned cur = lds_ld(&S->pubt);
-        while (cur < upto) {
-            if (__hip_atomic_compare_exchange_strong(&S->pubt, &cur, upto, __ATOMIC_RELAXED,
-                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                from = cur;
-                break;
-            }
-        }
-    }
-    from = (unsigned)__builtin_amdgcn_readlane((int)from, 0);
-    if (from >= upto) return;
-    // what the tasks' scans read was stored through or released by the committer wave before the
-    // block barrier this wave has passed: no fence here (fit_commit_mw.h mw_publish)
-    engine_publish(T.ctl, T.ring, from, upto, T.need, T.round, T.comp);
-}
 
 // The tile-readiness wait of fit_commit_mw.h for this shared layout: tiles are published just in
 // time (a helper that moves on to tile k publishes up to k + TL_AHEAD - 1 first), so a round that
@@ -155,7 +124,7 @@ __device__ __forceinline__ bool tm_tile_ready(const MwTiles& T, int tt, int& rea
     const int tile = __builtin_amdgcn_readfirstlane(tt) / SCAN_JOBS;
     if (tile < ready) return true;
     if (T.ring && (unsigned)tile + TL_AHEAD > lds_ld(&S->pubt))
-        tm_publish(T, S, min((unsigned)tile + TL_AHEAD, T.ntj));
+        commit_publish(T, S, min((unsigned)tile + TL_AHEAD, T.ntj));
     const unsigned* tdone = T.tdone;
     const unsigned need = T.need;
     for (unsigned sp = 0;; ++sp) {
@@ -203,6 +172,8 @@ __device__ __forceinline__ uint64_t tm_fit0(const Seg* L, const int4* PM, int cn
 
 
 typedef __attribute__((address_space(3))) v4i32 lds_v4i32;
+// (the low word of the generic pointer; fit_commit_mw.h's mw_lds_addr, an address-space cast, gives
+// tm_decider another register allocation)
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)p; }
 __device__ __forceinline__ void lds_st4(uint32_t a, v4i32 v) { *(lds_v4i32*)(uintptr_t)a = v; }
 __device__ __forceinline__ int32_t lds_ld1(uint32_t a) {
@@ -1007,21 +978,16 @@ __device__ __forceinline__ CommitResult commit_tl_window_mw(
     if (P.w > 0) {
         if (wave == 0) {
             const CommitResult r = tm_decider(P, S, lr, pmr, bitmap, RS, R, slab, out, outs, H);
-            if (threadIdx.x == 0) {
-                S->res[0] = r.done;
-                S->res[1] = r.stop;
-                S->res[2] = r.dirty;
-                S->res[3] = r.placed;
-            }
+            if (threadIdx.x == 0) put_result(S->res, r);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // placements, global-slab lists
         } else {
             tm_helper(P, S, lr, pmr, bitmap, RS, R, slab, hdr, cand, bnd, wjob, wave, H, T);
         }
     } else if (threadIdx.x == 0) {
-        S->res[0] = S->res[1] = S->res[2] = S->res[3] = 0;
+        put_result(S->res, CommitResult{0, 0, 0, 0});
     }
     __syncthreads();
-    const CommitResult r{S->res[0], S->res[1], S->res[2], S->res[3]};
+    const CommitResult r = get_result(S->res);
     // round end: LDS lists back to their slabs (the next scan reads them), headers for all
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int lane = threadIdx.x & 63;

@@ -1,5 +1,6 @@
 // fit_engine_ctl.h — control block and agent-scope hand-off primitives of the persistent
-// single-launch engines (k_engine: fit_persistent.hip; k_engine_tl: fit_timeline.hip).
+// single-launch engines (k_engine: fit_persistent.hip on fit_engine_frame.h; k_engine_tl:
+// fit_timeline.hip).
 // DESIGN.md §3.6.  Cross-workgroup hand-offs follow cdna_hip_programming.md §6 Guideline 16.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -865,7 +865,8 @@ namespace fitgpu {
 
 // ------------------------------------------------------------------------------ k_engine_tl
 // The whole backfill placement in ONE launch, on k_engine's protocol
-// (fit_persistent.hip, fit_engine_ctl.h): blocks [0, C) are committers — one wave each runs the
+// (fit_engine_frame.h, fit_engine_ctl.h; written out here: on the frame this kernel measured
+// 0.2-0.6 % slower at C5, profiles/engine_frame_ab.txt): blocks [0, C) are committers — one wave each runs the
 // component's rounds (publish its scan tiles to the device task ring, wait for them, commit the
 // window with commit_tl_window); blocks [C, C+W) are scan workers running scan_tile_tl.
 // Components advance at their own pace and their scans share the chip; no host round trips.
@@ -912,7 +913,6 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine_tl(
         unsigned used[2] = {0u, 0u};    // job tiles whose bounds the last round of each parity reset
                                         // and its scans lowered (k_engine's, fit_persistent.hip)
         int64_t evals = 0, placed = 0, rounds = 0, sr = 0, sd = 0, tc = 0, tw = 0;
-        bool fail = false;
         bool glob = false;  // the last window wrote a global-slab list (plain stores)
         while (cursor < S.jend) {
             const int w = min(win, S.jend - cursor);
@@ -971,7 +971,6 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine_tl(
                 if (lane == 0) reinterpret_cast<TmShared*>(smem)->pubt = npub;
                 acquire_agent();  // run lists written back by this block: CU-wide fresh view
                 if (lane == 0) s_fail = f;
-                fail = f;
             }
             __syncthreads();
             if (s_fail) break;  // block-uniform
@@ -1023,7 +1022,6 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine_tl(
             win = max(S.wmin, min(S.wmax, nw));
         }
         if (wave != 0) return;
-        (void)fail;  // every failure above recorded its own trip (or drained after another's)
         release_agent();  // last window's run lists / placements (kernel end also flushes)
         if (lane == 0) {
             co[c] = CompOut{evals, placed, cursor - S.jstart, rounds, sr, sd, tc, tw};

@@ -2,6 +2,8 @@
 
 Sizes are ones the oracle finishes in seconds; BASELINE.json's full C3 size is covered by the
 golden hashes in tests/golden (test_golden_gpu.py) and by size-independent properties."""
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -78,7 +80,8 @@ def test_fewer_keys_per_slice(ks_min, monkeypatch):
     assert st["components"] == 1
 
 
-@pytest.mark.parametrize("wmin,wmax", [(1, 1), (1, 8), (64, 64), (512, 65536)])
+# (64, 384): six job tiles, more than ENGINE_AHEAD, so the helpers publish the window's later tiles
+@pytest.mark.parametrize("wmin,wmax", [(1, 1), (1, 8), (64, 64), (64, 384), (512, 65536)])
 def test_window_policies_c2(wmin, wmax):
     nodes, jobs, parts = synth.make_config("c2", 512, 8192)
     check_parity(nodes, jobs, parts, window_min=wmin, window_max=wmax)
@@ -105,6 +108,13 @@ def test_c4_window_policies():
     nodes, jobs, parts = synth.make_config("c4", 512, 8192)
     for wmin, wmax in [(1, 1), (1, 8), (64, 64)]:
         check_parity(nodes, jobs, parts, kmax=8, window_min=wmin, window_max=wmax)
+    # one launch alternating the decider / helper commit (k = 1 windows) and the single-wave commit:
+    # every second block of 1,024 jobs becomes k = 1, and a block is longer than two windows of 384
+    single = (np.arange(jobs.j) // 1024) % 2 == 0
+    mixed = dataclasses.replace(jobs, nodes_k=np.where(single, 1, jobs.nodes_k).astype(np.uint16))
+    for b in range(1, jobs.j // 1024, 2):
+        assert mixed.nodes_k[b * 1024:(b + 1) * 1024].max() > 1
+    check_parity(nodes, mixed, parts, kmax=8, window_min=64, window_max=384)
 
 
 def test_multi_node_edge_cases():

@@ -50,7 +50,8 @@ def test_c5(nn, jj, engine, monkeypatch):
 
 
 @pytest.mark.parametrize("engine", ["persistent", "rounds"])
-@pytest.mark.parametrize("wmin,wmax", [(1, 1), (1, 8), (64, 64), (512, 65536)])
+# (64, 192): three job tiles, more than TL_AHEAD, so the helpers publish the window's last tile
+@pytest.mark.parametrize("wmin,wmax", [(1, 1), (1, 8), (64, 64), (64, 192), (512, 65536)])
 def test_c5_window_policies(wmin, wmax, engine, monkeypatch):
     monkeypatch.setenv("FIT_ENGINE", engine)
     nodes, tline, jobs, parts = synth.make_c5(256, 4096)
