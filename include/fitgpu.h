@@ -632,6 +632,50 @@ int fit_room_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen);
 
+/* ---- free capacity of every partition at every timeline slot ---------------
+ * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
+ * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced
+ * on the GPU from the run lists, without the dense read-back of fit_read_timeline.  Let T be the
+ * dense timeline fit_read_timeline returns, H the loaded horizon and mask[n] the loaded partition
+ * mask.  Slot (n, t) is OPEN iff T[n][t][c] >= 0 in all three columns; so a slot past the node's
+ * avail_min, a node in no partition and a slot with a column loaded negative are closed: the
+ * feasibility view of fit_place_tl and fit_hold_tl (such a slot takes no job, a zero demand
+ * included).  Row p * H + t describes, for partition p < parts and slot t < H, the nodes n with bit
+ * p of mask[n] set and (n, t) open.  `parts` (1..32) is the caller's choice and independent of
+ * fit_load_partitions: membership is the mask bit, as in fit_partition_free; mask bits >= parts are
+ * ignored, and a node in several partitions counts in each of them.  With no open member every
+ * field is 0 and the maxima are -1.  Read-only: the timeline, its headers and the node table are
+ * untouched, and two calls give the same bytes.  While a timeline is loaded fit_partition_free does
+ * not see the reservations the timeline writers made (they leave the node table untouched): row
+ * p * H + 0 is the capacity now. */
+typedef struct {             /* 40 bytes, 8-byte aligned                                           */
+    int64_t cpu, mem, gpu;   /* exact sums of T[n][t][c]; cannot overflow (2^29 nodes x 2^31)      */
+    int32_t nodes;           /* open member nodes at slot t                                        */
+    int32_t max_cpu, max_mem, max_gpu; /* column-wise maxima over them, -1 when nodes == 0.        */
+                             /* Upper bounds: a one-node job with cpu > max_cpu cannot run at t;   */
+                             /* the three maxima may come from different nodes                     */
+} fit_free;
+/* out: parts * H rows in host memory.  FIT_E_INVAL: NULL ctx or out, parts outside [1, 32].
+ * FIT_E_STATE: before fit_load_nodes; without a timeline loaded; on a context created with
+ * world > 1 or FIT_FLAG_COLLECTIVES.  A HIP error fails the call and leaves the timeline loaded:
+ * nothing was written.  Three bounded launches, no persistent grid: neither the per-GPU
+ * persistent-launch lock nor the watchdog. */
+int fit_free_tl(fit_ctx* ctx, int32_t parts, fit_free* out /* parts * H rows, row p * H + t */);
+/* Same with the rows written in HBM (out: device pointer, 8-byte aligned, else FIT_E_INVAL);
+ * complete on return. */
+int fit_free_tl_device(fit_ctx* ctx, int32_t parts, fit_free* out);
+/* Device time (HIP events) of the last successful fit_free_tl / fit_free_tl_device, as
+ * fit_advance_tl_ms; FIT_E_STATE before the first. */
+int fit_free_tl_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text, NUL-terminated into buf.  Host only: no device, no context.
+ * Returns the length written (without the NUL), or FIT_E_INVAL: NULL arguments, or a buffer too
+ * small for the text and its NUL (256 bytes always suffice).  The exact texts, <x> a decimal field
+ * of the row:
+ *   nodes > 0    "<nodes> nodes open: <cpu> cpus, <mem> MiB, <gpu> gpus free (at most <max_cpu> cpus,
+ *                 <max_mem> MiB, <max_gpu> gpus on one node)" — on one line
+ *   otherwise    "no open node" */
+int fit_free_message(const fit_free* r, char* buf, int32_t buflen);
+
 /* ---- ingest / demand helpers (host code, mirrors of the reference Go functions) -------- */
 /* ParseDuration (pkg/slurm-agent/parse.go:36-109): 0 ok, FIT_E_UNLIMITED, FIT_E_PARSE. */
 int fit_parse_duration(const char* s, int64_t* out_ns);

@@ -344,6 +344,11 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> atl_tc, atl_tm, atl_tg, atl_g;
     HBuf<int32_t> h_atl;
     double atl_ms = -1;
+    // fit_free_tl: the accumulator planes, the rows of the host entry point and the *_ms diagnostic
+    // 
+    DBuf<int64_t> free_acc;
+    DBuf<fit_free> free_rows;
+    double free_ms = -1;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -2573,6 +2578,55 @@ int fit_advance_tl_device(fit_ctx* c, int32_t a, const int32_t* tc, const int32_
 }
 
 int fit_advance_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::atl_ms, "fit_advance_tl", ms); }
+
+// fit_free_tl / fit_free_tl_device: read-only, so a HIP error fails the call
+// and the timeline stays loaded.  rows: device, parts * H of them, valid when the stream has drained.
+static int free_tl_impl(fit_ctx* c, int32_t parts, fit_free* rows) {
+    static_assert(sizeof(fit_free) == FREE_ROW_BYTES, "fit_free is 40 bytes");
+    const size_t n = (size_t)parts * c->tl_slots;
+    if (c->free_acc.ensure(n * (FREE_ROW_BYTES / sizeof(int64_t)))) return FIT_E_OOM;
+    int32_t chunk = FREE_CHUNK;  // FIT_FREE_CHUNK: measurements (tools/free_tl_bench.py)
+    if (const char* e = getenv("FIT_FREE_CHUNK")) chunk = std::max(1, std::min(atoi(e), FREE_MAX_CHUNK));
+    HIP_TRY(hipEventRecord(c->ev[0], c->st));
+    HIP_TRY(launch_free_tl(c->st, c->tlhdr.p, c->slab.p, c->nn, c->tl_slots, parts, chunk, c->free_acc.p, rows));
+    HIP_TRY(hipEventRecord(c->ev[1], c->st));
+    return 0;
+}
+static int free_tl_done(fit_ctx* c) {
+    float ms = 0.f;
+    HIP_TRY(hipStreamSynchronize(c->st));
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->free_ms = ms;
+    return 0;
+}
+static int check_free_tl_args(fit_ctx* c, int32_t parts, const fit_free* out) {
+    if (!c || !out) return fail(FIT_E_INVAL, "null argument");
+    if (parts < 1 || parts > 32) return fail(FIT_E_INVAL, "parts=%d (1..32)", parts);
+    return check_job_args(c, 0, {}, "fit_free_tl", 1);
+}
+
+int fit_free_tl(fit_ctx* c, int32_t parts, fit_free* out) {
+    int rc = check_free_tl_args(c, parts, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)parts * c->tl_slots;
+    if (c->free_rows.ensure(n)) return FIT_E_OOM;
+    rc = free_tl_impl(c, parts, c->free_rows.p);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->free_rows.p, sizeof(fit_free) * n, hipMemcpyDeviceToHost, c->st));
+    return free_tl_done(c);
+}
+
+int fit_free_tl_device(fit_ctx* c, int32_t parts, fit_free* out) {
+    int rc = check_free_tl_args(c, parts, out);
+    if (rc) return rc;
+    if ((uintptr_t)out & 7u) return fail(FIT_E_INVAL, "out is not 8-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    rc = free_tl_impl(c, parts, out);
+    return rc ? rc : free_tl_done(c);
+}
+
+int fit_free_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::free_ms, "fit_free_tl", ms); }
 
 int fit_read_timeline(fit_ctx* c, int32_t* cpu, int32_t* mem, int32_t* gpu) {
     if (!c) return fail(FIT_E_INVAL, "null ctx");

@@ -309,6 +309,18 @@ hipError_t launch_htl_hold(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, in
 hipError_t launch_htl_final(hipStream_t st, const uint16_t* jk, int32_t kmax, const int32_t* start, int32_t nj,
                             const int32_t* flag, int32_t* out_state, unsigned long long* tot);
 
+// ---- fit_free_tl (fit_free_tl.hip) -------------------------------------
+// Read-only: per (partition, slot) the sums, node count and column maxima over the open member nodes.
+constexpr int FREE_ROW_BYTES = 40;       // one fit_free row; the scratch planes take as much per row
+// Node positions per k_free_walk workgroup.  The walk takes one header after the other, each a
+// scalar load the next does not overlap, so its time goes with the chunk: at C5 0.27 ms at 64,
+// 0.35 at 128, 0.65 at 256, 1.05 at 512
+constexpr int FREE_CHUNK = 64;
+constexpr int FREE_MAX_CHUNK = 1 << 16;  // the most FIT_FREE_CHUNK (measurements) may ask for
+// scratch: FREE_ROW_BYTES * parts * H bytes; out: parts * H rows (row p * H + t); both 8-byte aligned
+hipError_t launch_free_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, int32_t nn, int32_t H, int32_t parts,
+                          int32_t chunk, void* scratch, void* out);
+
 // ---- fit_room (fit_room.hip) -------------------------------------------
 // The codes of include/fitgpu.h FIT_ROOM_* (engine.cpp asserts they agree); 5 is EX_NO_NODES.
 enum RoomCode : int32_t {

@@ -1053,4 +1053,17 @@ int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_free row as one line; the texts are fixed in include/fitgpu.h.  No device, no context.
+int fit_free_message(const fit_free* r, char* buf, int32_t buflen) {
+    if (!r || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s = "no open node";
+    if (r->nodes > 0)
+        s = std::to_string(r->nodes) + " nodes open: " + std::to_string(r->cpu) + " cpus, " + std::to_string(r->mem) +
+            " MiB, " + std::to_string(r->gpu) + " gpus free (at most " + std::to_string(r->max_cpu) + " cpus, " +
+            std::to_string(r->max_mem) + " MiB, " + std::to_string(r->max_gpu) + " gpus on one node)";
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 }  // extern "C"

@@ -37,7 +37,7 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta, FitEtaK, FIT_MAX_K,
                    FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
                    FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom,
-                   FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED)
+                   FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED, FitFree)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -55,6 +55,7 @@ __all__ = [
     "room_message", "ROOM_DTYPE", "FitRoom", "FIT_ROOM_SOME", "FIT_ROOM_PARTITION", "FIT_ROOM_LIMIT_TIME",
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
     "FIT_HOLD_HELD", "FIT_HOLD_REFUSED", "FIT_HOLD_SKIPPED",
+    "free_message", "FREE_DTYPE", "FitFree",
 ]
 
 
@@ -400,6 +401,22 @@ def room_message(row) -> str:
     r = FitRoom(*(int(get(n)) for n, _ in FitRoom._fields_))
     buf = C.create_string_buffer(256)
     n = check(lib().fit_room_message(C.byref(r), buf, len(buf)), "fit_room_message")
+    return buf.raw[:n].decode()
+
+
+# ---------------------------------------------------------------------------------- free
+# one fit_free row (include/fitgpu.h), 40 bytes: three int64 sums, then nodes and the three maxima:
+# what Engine.free_tl returns
+FREE_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.int32) for n, t in FitFree._fields_])
+
+
+def free_message(row) -> str:
+    """A fit_free row (an element of a free_tl() result, or any mapping / object with its fields) as
+    one line of text (fit_free_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    r = FitFree(*(int(get(n)) for n, _ in FitFree._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_free_message(C.byref(r), buf, len(buf)), "fit_free_message")
     return buf.raw[:n].decode()
 
 
@@ -816,6 +833,31 @@ class Engine:
             return 0.0
         ms = C.c_double()
         check(lib().fit_room_ms(self._h, C.byref(ms)), "fit_room_ms")
+        return ms.value
+
+    # ---- free capacity per partition and slot --------------------------------
+    def free_tl(self, parts: int):
+        """The capacity profile of the current timeline (fit_free_tl): a structured array of
+        FREE_DTYPE rows [parts, H] (cpu, mem, gpu, nodes, max_cpu, max_mem, max_gpu), row [p, t] over
+        the nodes with mask bit p that are open at slot t.  Changes nothing."""
+        parts = int(parts)
+        # parts outside 1..32 or no timeline is the library's error, before it writes a row
+        out = np.zeros((min(max(parts, 1), 32), max(getattr(self, "slots", 0), 1)), FREE_DTYPE)
+        check(lib().fit_free_tl(self._h, parts, _ptr(out)), "fit_free_tl")
+        return out
+
+    def free_tl_device(self, parts: int, out):
+        """The rows written into out, a torch tensor resident on this GPU (parts * H rows of 40 bytes,
+        FREE_DTYPE's layout, 8-byte aligned: an int64 tensor of parts * H * 5 words will do).  Returns
+        the device time of its launches in ms (HIP events on the context's stream, fit_free_tl_ms)."""
+        check(lib().fit_free_tl_device(self._h, int(parts), _ptr(out)), "fit_free_tl_device")
+        return self.free_tl_ms()
+
+    def free_tl_ms(self):
+        """Device time in ms of the last successful free_tl / free_tl_device (HIP events on the
+        context's stream, fit_free_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_free_tl_ms(self._h, C.byref(ms)), "fit_free_tl_ms")
         return ms.value
 
     def read_timeline(self):

@@ -48,6 +48,7 @@ EXPORTS = [
     "fit_unplace_tl", "fit_unplace_tl_device", "fit_unplace_tl_ms",
     "fit_advance_tl", "fit_advance_tl_device", "fit_advance_tl_ms",
     "fit_hold_tl", "fit_hold_tl_device", "fit_hold_tl_ms",
+    "fit_free_tl", "fit_free_tl_device", "fit_free_tl_ms", "fit_free_message",
 ]
 
 
@@ -130,6 +131,11 @@ class FitRoom(C.Structure):
     _fields_ = [("code", C.c_int32), ("members", C.c_int32), ("nodes", C.c_int32), ("best", C.c_int32),
                 ("copies", C.c_int64), ("best_node", C.c_int32), ("by_gpu", C.c_int32), ("by_cpu", C.c_int32),
                 ("by_mem", C.c_int32)]
+
+
+class FitFree(C.Structure):  # fit_free: one (partition, slot) row of fit_free_tl, 40 bytes
+    _fields_ = [("cpu", C.c_int64), ("mem", C.c_int64), ("gpu", C.c_int64), ("nodes", C.c_int32),
+                ("max_cpu", C.c_int32), ("max_mem", C.c_int32), ("max_gpu", C.c_int32)]
 
 
 FIT_TABLE_STATE = 1  # fit_node_table.flags: part_mask carries node State (include/fitgpu.h)
@@ -225,6 +231,10 @@ def lib() -> C.CDLL:
         for name in ("fit_hold_tl", "fit_hold_tl_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, i32, P, P, P, C.POINTER(i64), C.POINTER(i64)]
         L.fit_hold_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
+        for name in ("fit_free_tl", "fit_free_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P]
+        L.fit_free_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_free_message.argtypes = [C.POINTER(FitFree), C.c_char_p, i32]
         L.fit_read_timeline.argtypes = [P, P, P, P]
         L.fit_ingest_nodes.argtypes = [C.c_char_p, C.c_char_p, i32, i32, P, P, P, P, P, C.c_char_p, i32]
         L.fit_expand_hostlist.argtypes = [C.c_char_p, C.c_char_p, i32]

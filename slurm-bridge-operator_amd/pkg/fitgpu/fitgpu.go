@@ -77,7 +77,10 @@ func check(rc C.int) error {
 
 // Engine wraps one fit_ctx (one GPU).  Not safe for concurrent use; the VK provider serialises
 // its 10 PodSyncWorkers through a batcher (INTEGRATION.md).
-type Engine struct{ ctx *C.fit_ctx }
+type Engine struct {
+	ctx   *C.fit_ctx
+	slots int // horizon of the last successful LoadTimeline (FreeTL sizes its rows by it)
+}
 
 func New(device int) (*Engine, error) {
 	opts := C.fit_opts{device: C.int32_t(device), world: 1}
@@ -266,16 +269,22 @@ func (e *Engine) LoadTimeline(slots, slotMin int, r Releases) error {
 	if len(r.Off) > 0 && int(r.Off[len(r.Off)-1]) > len(r.Slot) {
 		return fmt.Errorf("fitgpu: Off ends at %d but there are %d release events", r.Off[len(r.Off)-1], len(r.Slot))
 	}
+	var err error
 	if len(r.Off) == 0 {
-		return check(C.fit_load_timeline(e.ctx, C.int32_t(slots), C.int32_t(slotMin), nil, nil, nil, nil, nil))
+		err = check(C.fit_load_timeline(e.ctx, C.int32_t(slots), C.int32_t(slotMin), nil, nil, nil, nil, nil))
+	} else {
+		var s, c, m, g *C.int32_t
+		if len(r.Slot) > 0 {
+			s, c = (*C.int32_t)(unsafe.Pointer(&r.Slot[0])), (*C.int32_t)(unsafe.Pointer(&r.CPU[0]))
+			m, g = (*C.int32_t)(unsafe.Pointer(&r.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&r.GPU[0]))
+		}
+		err = check(C.fit_load_timeline(e.ctx, C.int32_t(slots), C.int32_t(slotMin),
+			(*C.int32_t)(unsafe.Pointer(&r.Off[0])), s, c, m, g))
 	}
-	var s, c, m, g *C.int32_t
-	if len(r.Slot) > 0 {
-		s, c = (*C.int32_t)(unsafe.Pointer(&r.Slot[0])), (*C.int32_t)(unsafe.Pointer(&r.CPU[0]))
-		m, g = (*C.int32_t)(unsafe.Pointer(&r.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&r.GPU[0]))
+	if err == nil {
+		e.slots = slots
 	}
-	return check(C.fit_load_timeline(e.ctx, C.int32_t(slots), C.int32_t(slotMin),
-		(*C.int32_t)(unsafe.Pointer(&r.Off[0])), s, c, m, g))
+	return err
 }
 
 // RunningJob is one job the caller knows is running (the virtual kubelet's own pods): its engine
@@ -608,6 +617,64 @@ func RoomMessage(r Room) string {
 		by_gpu: C.int32_t(r.ByGPU), by_cpu: C.int32_t(r.ByCPU), by_mem: C.int32_t(r.ByMem)}
 	buf := make([]byte, 256)
 	n := C.fit_room_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
+// Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
+// nodes that are open there (DESIGN.md §2k).
+type Free struct {
+	CPU    int64 // free cpus, summed over the open members
+	Mem    int64 // free MiB
+	GPU    int64 // free GPUs
+	Nodes  int32 // open member nodes at the slot
+	MaxCPU int32 // the most free cpus on one of them, -1 when Nodes == 0: a one-node job that asks for
+	MaxMem int32 // more cannot run at the slot; the three maxima may come from different nodes
+	MaxGPU int32
+}
+
+func goFree(r *C.fit_free) Free {
+	return Free{CPU: int64(r.cpu), Mem: int64(r.mem), GPU: int64(r.gpu), Nodes: int32(r.nodes),
+		MaxCPU: int32(r.max_cpu), MaxMem: int32(r.max_mem), MaxGPU: int32(r.max_gpu)}
+}
+
+// FreeTL gives the free capacity of partitions 0 .. parts-1 (the node table's mask bits, 1..32 of
+// them) at every slot of the loaded timeline, reservations included (fit_free_tl): out[p][t].  It
+// changes nothing.  out[p][0] is the capacity now: while a timeline is loaded PartitionFree does
+// not see the timeline's reservations.
+func (e *Engine) FreeTL(parts int) ([][]Free, error) {
+	if parts < 1 || parts > 32 {
+		return nil, fmt.Errorf("fitgpu: parts %d outside 1..32", parts)
+	}
+	h := e.slots
+	if h < 1 {
+		h = 1 // no LoadTimeline yet: the library refuses the call before it writes a row
+	}
+	rows := make([]C.fit_free, parts*h)
+	rc := C.fit_free_tl(e.ctx, C.int32_t(parts), &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([][]Free, parts)
+	for p := range out {
+		out[p] = make([]Free, h)
+		for t := range out[p] {
+			out[p][t] = goFree(&rows[p*h+t])
+		}
+	}
+	return out, nil
+}
+
+// FreeMessage is the row as one line (fit_free_message: "3 nodes open: 12 cpus, 3000 MiB, 2 gpus
+// free (at most 8 cpus, 2000 MiB, 1 gpus on one node)", or "no open node").
+func FreeMessage(r Free) string {
+	c := C.fit_free{cpu: C.int64_t(r.CPU), mem: C.int64_t(r.Mem), gpu: C.int64_t(r.GPU), nodes: C.int32_t(r.Nodes),
+		max_cpu: C.int32_t(r.MaxCPU), max_mem: C.int32_t(r.MaxMem), max_gpu: C.int32_t(r.MaxGPU)}
+	buf := make([]byte, 256)
+	n := C.fit_free_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
 	if n < 0 {
 		return ""
 	}
