@@ -127,18 +127,6 @@ struct ClsLds {
     ClsRec sink[64];                 // the decider's lanes 1..63 store here instead of branching
 };
 
-__device__ __forceinline__ unsigned lds_ld(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_st(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// v_writelane_b32: lane `l` of `old` := uniform x (no clang builtin on this toolchain)
-__device__ __forceinline__ int32_t cls_writelane(int32_t x, int l, int32_t old) {
-    int32_t r;
-    asm("v_writelane_b32 %0, %1, m0" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(x)), "{m0}"(l), "0"(old));
-    return r;
-}
 __device__ __forceinline__ uint4 ld_prog(const unsigned* p) {  // the bookkeepers' progress words
     uint4 v;
     v.x = lds_ld(p);
@@ -147,8 +135,6 @@ __device__ __forceinline__ uint4 ld_prog(const unsigned* p) {  // the bookkeeper
     v.w = 0u;
     return v;
 }
-__device__ __forceinline__ void cls_acq() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
-__device__ __forceinline__ void cls_rel() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
 
 // SPEC §2 key of a row for a demand; the walltime test only when WALL (sets are walltime-free)
 template <bool WALL>
@@ -156,15 +142,8 @@ __device__ __forceinline__ uint64_t cls_key(const int4 r, int32_t dc, int32_t dm
                                             uint32_t pos) {
     const int32_t a = r.x - dc, b = r.y - dm, g = r.z - dg;
     const bool ok = WALL ? ((a | b | g | (r.w - w)) >= 0) : ((a | b | g) >= 0);
-    const uint32_t sc = (min((uint32_t)g, 255u) << 24) | (min((uint32_t)a, 4095u) << 12) |
-                        min((uint32_t)b >> 10, 4095u);
+    const uint32_t sc = fit_score(a, b, g);
     return ok ? (((uint64_t)sc << 32) | pos) : KEY_INF;
-}
-
-__device__ __forceinline__ uint64_t rdlane64(uint64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // ---- classify: a dense class id per job and component (two launches over all jobs) -----------
@@ -414,7 +393,7 @@ __device__ __forceinline__ bool cls_drain(ClsLds* S, unsigned ncommit) {
         while (lds_ld(&S->ctl.prog[b]) != ncommit)
             if (++sp > CLS_SPIN) return false;
     }
-    cls_acq();
+    lds_acquire();
     return true;
 }
 
@@ -426,7 +405,7 @@ __device__ __forceinline__ void cls_request(ClsLds* S, ClsDec& D, unsigned op, u
         S->ctl.op_k = k;
         S->ctl.pool_n = 0;
     }
-    cls_rel();
+    lds_release();
     if ((threadIdx.x & 63) == 0) lds_st(&S->ctl.op_epoch, ++D.epoch);
     else ++D.epoch;
 }
@@ -553,7 +532,7 @@ __global__ __launch_bounds__(CLS_THREADS) void k_class(
                 key = key == m ? KEY_INF : key;
                 m = wave_min_key_lane(key, ln);
                 if (m == KEY_INF) break;
-                pkl = (uint32_t)cls_writelane((int)(uint32_t)m, j, (int)pkl);
+                pkl = (uint32_t)writelane((int)(uint32_t)m, j, (int)pkl);
                 kth = m;
                 np = j + 1;
             }

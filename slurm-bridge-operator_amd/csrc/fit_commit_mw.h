@@ -52,9 +52,11 @@
 // On gfx950 (no threadgroup split) a workgroup-scope release / acquire on LDS is an
 // `s_waitcnt lgkmcnt(0)` before the store / after the load (checked in the ISA); both sit where
 // the counter is already drained, so the protocol costs no cycles on the decider's chain.
+// (Primitives: fit_wave.h — lds_*, global views, write-through loads, DPP minima; key: fit_key.h.)
 #pragma once
 #include "fit_common.h"
 #include "fit_engine_ctl.h"
+#include "fit_wave.h"  // LDS hand-offs and addresses, global views, fused DPP minima, writelane
 
 namespace fitgpu {
 
@@ -187,16 +189,6 @@ __device__ unsigned long long g_mw[64][MW_NSTAMP];
 #define MW_ADD(I_, V_)
 #endif
 
-// ---- LDS hand-off primitives (workgroup scope, LDS only) ------------------------------------
-__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
-__device__ __forceinline__ void lds_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
-
 // The commit's waits — the helpers' waits for scan tiles, and the decider <-> helper waits inside
 // the block — keep round 4's spin bound (MW_SPIN_LIMIT polls, ≈ 4-8 s).  Every other wait of the
 // engine has a time deadline (fit_engine_ctl.h WaitClock), and those bound what the commit waits
@@ -244,113 +236,9 @@ struct MwTiles {
 #define ENGINE_AHEAD 4  // 0: every tile of the window published up front
 #endif
 
-// global address-space views of the helper's buffers: a plain (generic) pointer in a non-inlined
-// function compiles to flat loads, which also count in lgkmcnt — every LDS wait would then drain
-// the prefetched job stream
-#ifdef __HIP_DEVICE_COMPILE__
-#define GAS __attribute__((address_space(1)))
-#else  // (the host pass only parses device code)
-#define GAS
-#endif
-template <class T>
-__device__ __forceinline__ const GAS T* gview(const T* p) {
-    return (const GAS T*)p;
-}
-
-typedef int32_t v4i32 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ NodeRec ld_node(const GAS NodeRec* p) {
-    const GAS v4i32* q = (const GAS v4i32*)p;
-    const v4i32 a = q[0], b = q[1];
-    NodeRec r;
-    r.cpu = a.x;
-    r.mem = a.y;
-    r.gpu = a.z;
-    r.avail = a.w;
-    r.mask = (uint32_t)b.x;
-    r.orig = b.y;
-    r.pad0 = b.z;
-    r.pad1 = b.w;
-    return r;
-}
-
-__device__ __forceinline__ JobRec ld_job(const GAS JobRec* p) {
-    const GAS v4i32* q = (const GAS v4i32*)p;
-    const v4i32 a = q[0], b = q[1];
-    JobRec r;
-    r.q = a.x;
-    r.cpu = a.y;
-    r.mem = a.z;
-    r.gpu = a.w;
-    r.wall = b.x;
-    r.pbit = (uint32_t)b.y;
-    r.k = b.z;
-    r.pad = b.w;
-    return r;
-}
-
-// Write-through reads of a scan tile's outputs (candidates, bound, job row), which the scan workers
-// store through (sc1) and count with an agent-scope add: a helper that has seen the tile's count
-// reach its target in a relaxed agent poll reads them with sc1 loads, which bypass this CU's L1,
-// instead of an acquire fence (≈1.7 us, once per tile per helper, and on every round's start:
-// cdna_hip_programming.md §6 Guideline 16; MI355X_MICROARCH.md hand-off table, row 1 — one block
-// per CU, 8-B sc1 stores and loads, the polling wave loads after its poll matched).
-__device__ __forceinline__ uint64_t ld_through(const GAS uint64_t* p) {
-    return __hip_atomic_load(const_cast<GAS uint64_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ JobRec ld_job_through(const GAS JobRec* p) {
-    const GAS uint64_t* q = (const GAS uint64_t*)p;
-    const uint64_t w0 = ld_through(q), w1 = ld_through(q + 1), w2 = ld_through(q + 2), w3 = ld_through(q + 3);
-    JobRec r;
-    r.q = (int32_t)(uint32_t)w0;
-    r.cpu = (int32_t)(uint32_t)(w0 >> 32);
-    r.mem = (int32_t)(uint32_t)w1;
-    r.gpu = (int32_t)(uint32_t)(w1 >> 32);
-    r.wall = (int32_t)(uint32_t)w2;
-    r.pbit = (uint32_t)(w2 >> 32);
-    r.k = (int32_t)(uint32_t)w3;
-    r.pad = (int32_t)(uint32_t)(w3 >> 32);
-    return r;
-}
-
-// a VGPR zero the compiler cannot see through: keeps uniform loads of data written by other
-// workgroups in this launch on the vector path (vmcnt, in order) instead of the scalar cache
-__device__ __forceinline__ int opaque_zero() {
-    int z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-
-// A dynamic-LDS pointer the compiler cannot re-derive: in an out-of-line function the constant
-// shared base is otherwise rematerialised from the dynlds offset table (an s_load + lgkmcnt(0)
-// wait) on every loop iteration; laundered through an SGPR it is computed once.  The round trip
-// through address space 3 keeps every access a ds_* instruction.
-template <class T>
-__device__ __forceinline__ T* lds_opaque(T* p) {
-    uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p;
-    asm volatile("" : "+s"(a));
-    return (T*)(__attribute__((address_space(3))) T*)(uintptr_t)a;
-}
-
-// the 32-bit LDS address of an object in shared memory (what a ds_* instruction takes)
-template <class T>
-__device__ __forceinline__ uint32_t mw_lds_addr(T* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) T*)p;
-}
-
-// lds_opaque for an LDS address that depends on runtime values: made uniform first, so that it
-// can live in an SGPR
-template <class T>
-__device__ __forceinline__ T* tm_lds(T* p) {
-    typedef __attribute__((address_space(3))) T* Lds;
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane((int)mw_lds_addr(p));  // uniform
-    return lds_opaque((T*)(Lds)(uintptr_t)a);
-}
-
 // The plan copied into SGPRs: an out-of-line function receives it through a generic pointer, and
 // fields loaded that way sit in VGPRs, so the compiler cannot prove the job loop uniform (it
 // would run it under exec masks with its counter in a VGPR).
-__device__ __forceinline__ int32_t rfl(int32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ CompPlan plan_sgpr(const CompPlan& q) {
     CompPlan p;
     p.nb = rfl(q.nb);
@@ -368,115 +256,6 @@ __device__ __forceinline__ CompPlan plan_sgpr(const CompPlan& q) {
     p.slot0 = rfl(q.slot0);
     return p;
 }
-
-__device__ __forceinline__ uint64_t mw_key(int32_t cf, int32_t mf, int32_t gf, int32_t av,
-                                           uint32_t mask, uint32_t pos, int32_t jc, int32_t jm,
-                                           int32_t jg, int32_t jw, uint32_t jp) {
-    const int32_t dc = cf - jc, dm = mf - jm, dg = gf - jg, da = av - jw;
-    const bool ok = (dc | dm | dg | da) >= 0 && (mask & jp);
-    const uint32_t sc = (min((uint32_t)dg, 255u) << 24) | (min((uint32_t)dc, 4095u) << 12) |
-                        min((uint32_t)dm >> 10, 4095u);
-    return ok ? (((uint64_t)sc << 32) | pos) : KEY_INF;
-}
-
-// ---- DPP building blocks ---------------------------------------------------------------------
-template <int CTRL, int ROWMASK = 0xf>
-__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
-    if constexpr (ROWMASK == 0xf)  // every lane has a source: a plain DPP move
-        return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, false);
-    else  // lanes of rows outside the mask keep their value
-        return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWMASK, 0xf, false);
-}
-// one 64-bit min step against the DPP-permuted value (2 moves, a 64-bit compare, 2 selects)
-template <int CTRL, int ROWMASK = 0xf>
-__device__ __forceinline__ uint64_t dpp_min64(uint64_t v) {
-    const uint32_t lo = dpp32<CTRL, ROWMASK>((uint32_t)v), hi = dpp32<CTRL, ROWMASK>((uint32_t)(v >> 32));
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    return o < v ? o : v;
-}
-// minimum over each group of 8 lanes, in all 8 of them: quad swaps, then the half-row mirror
-__device__ __forceinline__ uint64_t min8_64(uint64_t v) {
-    v = dpp_min64<0xb1>(v);   // quad_perm [1,0,3,2]
-    v = dpp_min64<0x4e>(v);   // quad_perm [2,3,0,1]
-    return dpp_min64<0x141>(v);  // row_half_mirror
-}
-// Fused DPP ALU ops in inline asm (hipcc emits a DPP move plus the ALU op for the builtins).
-// Each string opens with the two wait states a DPP read of a VGPR written by the previous VALU
-// instruction needs (cdna_hip_programming.md: DPP hazard; `s_nop 1`).
-#define MW_DPP_MIN(v, CTL) asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 " CTL : "+v"(v))
-__device__ __forceinline__ uint32_t dppmin_qp1032(uint32_t v) { MW_DPP_MIN(v, "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"); return v; }
-__device__ __forceinline__ uint32_t dppmin_qp2301(uint32_t v) { MW_DPP_MIN(v, "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"); return v; }
-__device__ __forceinline__ uint32_t dppmin_hmirror(uint32_t v) { MW_DPP_MIN(v, "row_half_mirror row_mask:0xf bank_mask:0xf"); return v; }
-__device__ __forceinline__ uint32_t dppmin_mirror(uint32_t v) { MW_DPP_MIN(v, "row_mirror row_mask:0xf bank_mask:0xf"); return v; }
-__device__ __forceinline__ uint32_t dppmin_bcast15(uint32_t v) { MW_DPP_MIN(v, "row_bcast:15 row_mask:0xa bank_mask:0xf"); return v; }
-__device__ __forceinline__ uint32_t dppmin_bcast31(uint32_t v) { MW_DPP_MIN(v, "row_bcast:31 row_mask:0xc bank_mask:0xf"); return v; }
-template <int CTRL, int ROWMASK = 0xf>
-__device__ __forceinline__ uint32_t dpp_min32(uint32_t v) {
-    if constexpr (CTRL == 0xb1) return dppmin_qp1032(v);
-    else if constexpr (CTRL == 0x4e) return dppmin_qp2301(v);
-    else if constexpr (CTRL == 0x141) return dppmin_hmirror(v);
-    else if constexpr (CTRL == 0x140) return dppmin_mirror(v);
-    else if constexpr (CTRL == 0x142) return dppmin_bcast15(v);
-    else return dppmin_bcast31(v);
-}
-// d = src ^ (x rotated by K within its row of 16 lanes); NOP: src of the DPP just written
-template <int K, bool NOP>
-__device__ __forceinline__ uint32_t dpp_ror_xor(uint32_t x, uint32_t y) {
-    uint32_t d;
-    if constexpr (NOP)
-        asm volatile("s_nop 1\n\tv_xor_b32_dpp %0, %1, %2 row_ror:%3 row_mask:0xf bank_mask:0xf"
-                     : "=v"(d) : "v"(x), "v"(y), "i"(K));
-    else
-        asm volatile("v_xor_b32_dpp %0, %1, %2 row_ror:%3 row_mask:0xf bank_mask:0xf"
-                     : "=v"(d) : "v"(x), "v"(y), "i"(K));
-    return d;
-}
-// 64-bit minimum over each group of 8 lanes, in all 8: the 32-bit minimum of the high words,
-// then of the low words among the lanes holding it (fused DPP mins, no 64-bit compares)
-__device__ __forceinline__ uint64_t min8_2pass(uint64_t v) {
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    uint32_t mh = dpp_min32<0xb1>(hi);
-    mh = dpp_min32<0x4e>(mh);
-    mh = dpp_min32<0x141>(mh);
-    uint32_t ml = hi == mh ? lo : 0xffffffffu;
-    ml = dpp_min32<0xb1>(ml);
-    ml = dpp_min32<0x4e>(ml);
-    ml = dpp_min32<0x141>(ml);
-    return ((uint64_t)mh << 32) | ml;
-}
-// 32-bit minimum over the wave, valid in lane 63
-__device__ __forceinline__ uint32_t wave_min32_l63(uint32_t v) {
-    v = dpp_min32<0xb1>(v);
-    v = dpp_min32<0x4e>(v);
-    v = dpp_min32<0x141>(v);
-    v = dpp_min32<0x140>(v);
-    v = dpp_min32<0x142, 0xa>(v);
-    return dpp_min32<0x143, 0xc>(v);
-}
-// minimum over the wave, valid in lane 63
-__device__ __forceinline__ uint64_t wave_min64_l63(uint64_t v) {
-    v = dpp_min64<0xb1>(v);
-    v = dpp_min64<0x4e>(v);
-    v = dpp_min64<0x141>(v);       // row_half_mirror: 8-lane groups
-    v = dpp_min64<0x140>(v);       // row_mirror: whole rows of 16
-    v = dpp_min64<0x142, 0xa>(v);  // row_bcast:15 → rows 1 and 3
-    return dpp_min64<0x143, 0xc>(v);  // row_bcast:31 → rows 2 and 3
-}
-
-// v_writelane_b32: lane `l` of `old` := SGPR `x` (no clang builtin on this toolchain)
-__device__ __forceinline__ int32_t writelane(int32_t x, int l, int32_t old) {
-    int32_t r;
-    // the lane select goes through M0 (one SGPR operand per VALU instruction on gfx9)
-    asm("v_writelane_b32 %0, %1, m0" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(x)), "{m0}"(l), "0"(old));
-    return r;
-}
-template <int L>
-__device__ __forceinline__ int32_t writelane_c(int32_t x, int32_t old) {  // compile-time lane
-    int32_t r;
-    asm("v_writelane_b32 %0, %1, %2" : "=v"(r) : "s"(__builtin_amdgcn_readfirstlane(x)), "i"(L), "0"(old));
-    return r;
-}
-__device__ __forceinline__ int32_t readlane(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
 // One CommitResult through the shared block's res[4]: one lane puts it, every wave gets it after
 // the next barrier.
@@ -600,12 +379,6 @@ __device__ __forceinline__ bool mw_skip_live(const MwTiles& T, const CompPlan& P
 // The tile hand-off copied into SGPRs: mw_helper receives it in private memory (a by-value
 // aggregate of an out-of-line callee), and every field read from there is a scratch load whose
 // vmcnt wait would drain the helper's prefetched job stream.
-template <class Q>
-__device__ __forceinline__ Q* rfl_ptr(Q* p) {
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    return (Q*)(uintptr_t)(((uint64_t)(uint32_t)rfl((int32_t)(v >> 32)) << 32) |
-                           (uint32_t)rfl((int32_t)(uint32_t)v));
-}
 __device__ __forceinline__ MwTiles tiles_sgpr(const MwTiles& T) {
     return MwTiles{rfl_ptr(T.tdone), (unsigned)rfl((int32_t)T.need), rfl_ptr(T.ring),
                    rfl_ptr(T.ctl), (unsigned)rfl((int32_t)T.round), (unsigned)rfl((int32_t)T.comp),
@@ -656,18 +429,6 @@ __device__ __forceinline__ void mw_sort(uint64_t (&q)[N]) {
 // stop at nmax_ (a uniform branch: round 4, C3 26.39 -> 26.02 ms, C2 14.95 -> 14.75 ms — a shorter
 // helper record leaves the decider's SIMD and the LDS to the decider sooner); rounds past the last
 // entry take nothing (stopping there too was slower)
-__device__ __forceinline__ uint32_t wave_min32_all(uint32_t v) {
-    v = dpp_min32<0xb1>(v);
-    v = dpp_min32<0x4e>(v);
-    v = dpp_min32<0x141>(v);
-    v = dpp_min32<0x140>(v);  // every lane: its row's minimum
-    {
-        const auto p = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        v = min((uint32_t)p[0], (uint32_t)p[1]);
-    }
-    const auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return min((uint32_t)p[0], (uint32_t)p[1]);
-}
 #define MW_EXTRACT                                                                             \
         _Pragma("unroll") for (int i_ = 0; i_ < MW_M; ++i_) {                                  \
             if (i_ >= nmax_) break; /* uniform: a record needs nmax_ items at most */          \
@@ -774,9 +535,9 @@ __device__ __forceinline__ uint32_t wave_min32_all(uint32_t v) {
             const int u_ = u * 64 + lane;                                                      \
             if (u * 64 < nu_) { /* uniform: rows [0, nu) exist */                              \
                 wr_[u] = S->rows[u_ < nu_ ? u_ : 0];                                           \
-                const uint64_t y_ = mw_key(wr_[u].cpu, wr_[u].mem, wr_[u].gpu, wr_[u].avail,   \
-                                           wr_[u].mask, wr_[u].pos, J_.cpu, J_.mem, J_.gpu,    \
-                                           J_.wall, J_.pbit);                                  \
+                const uint64_t y_ = fit_key(wr_[u].cpu, wr_[u].mem, wr_[u].gpu, wr_[u].avail,  \
+                                            wr_[u].mask, wr_[u].pos, J_.cpu, J_.mem, J_.gpu,   \
+                                            J_.wall, J_.pbit);                                 \
                 xd[u] = u_ < nu_ && y_ <= Bd_ ? y_ : KEY_INF;                                  \
             }                                                                                  \
         }                                                                                      \
@@ -933,7 +694,6 @@ struct MwRing {
     int32_t slot;  // dirty slot
 };
 
-typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
 struct MwRecRegs {  // one record as this lane sees it: header (every lane) and item lane & 7
     v4u32 h0, h1, h2;  // {ready, v, n, q}, {cpu, mem, gpu, wall}, {pbit, -, B lo, B hi}
     v4u32 i0, i1, i2;  // {pos, score, tag, orig}, {cpu, mem, gpu, avail}, {mask, chk_addr, chk_mask, chk_thr}
@@ -965,9 +725,6 @@ __device__ unsigned long long g_seg[8];
 #define MW_SEG(D_, i)
 #endif
 
-__device__ __forceinline__ const __attribute__((address_space(3))) v4u32* lds4(const void* p) {
-    return (const __attribute__((address_space(3))) v4u32*)(uintptr_t)p;
-}
 __device__ __forceinline__ void mw_read_rec(const MwRec* R, int i8, MwRecRegs& x) {
     const __attribute__((address_space(3))) v4u32* hp = lds4(&R->h);
     const __attribute__((address_space(3))) v4u32* ip = lds4(&R->it[i8]);
@@ -1105,8 +862,8 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         const uint32_t pv = *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)x.i2.y;
         // live ring rows at their current state
         const bool live = R.b.w >= v;
-        const uint64_t rk0 = mw_key(R.a.x, R.a.y, R.a.z, R.a.w, (uint32_t)R.b.x, (uint32_t)R.b.y,
-                                    jc, jm, jg, jw, jp);
+        const uint64_t rk0 = fit_key(R.a.x, R.a.y, R.a.z, R.a.w, (uint32_t)R.b.x, (uint32_t)R.b.y,
+                                     jc, jm, jg, jw, jp);
         const uint64_t rkey = live ? rk0 : KEY_INF;
         const uint32_t ip = x.i0.x;
         const bool stale = (pv & x.i2.z) >= x.i2.w;

@@ -1,7 +1,7 @@
 // fit_commit_tl_mw.h — the backfill commit (SPEC §2b, config C5) of one component's window by a
 // whole 8-wave workgroup, on the decider / helper split of fit_commit_mw.h.
 // Included by fit_timeline.hip after the run-list primitives it uses (tl_key, tl_eval4,
-// tl_walk_wave, tl_reserve_lds, tl_reserve_any, wave_scan_min).
+// tl_walk_wave, tl_reserve_lds, tl_reserve_any); the lane, wave and LDS primitives are fit_wave.h's.
 //
 // Wave 0 is the DECIDER, waves 1..7 are HELPERS.  Helper h pre-resolves jobs t = h-1 (mod 7)
 // against a snapshot of the dirty state taken once the decider has resolved v >= t - 7 jobs: it
@@ -168,23 +168,6 @@ __device__ __forceinline__ uint64_t tm_fit0(const Seg* L, const int4* PM, int cn
     const int4 pk = PM[min(k, R - 1)];
     fit0 = ok && pk.x >= jc && pk.y >= jm && pk.z >= jg;
     return fit0 ? tl_key(0, pk.x, pk.y, pk.z, jc, jm, jg, pos) : KEY_INF;
-}
-
-
-typedef __attribute__((address_space(3))) v4i32 lds_v4i32;
-// (the low word of the generic pointer; fit_commit_mw.h's mw_lds_addr, an address-space cast, gives
-// tm_decider another register allocation)
-__device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)p; }
-__device__ __forceinline__ void lds_st4(uint32_t a, v4i32 v) { *(lds_v4i32*)(uintptr_t)a = v; }
-__device__ __forceinline__ int32_t lds_ld1(uint32_t a) {
-    return *(const __attribute__((address_space(3))) int32_t*)(uintptr_t)a;
-}
-// the previous lane's value (lane 0: `first`) / the next lane's (lane 63: `last`): DPP wave shifts
-__device__ __forceinline__ int32_t wave_shr1(int32_t v, int32_t first) {
-    return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int32_t wave_shl1(int32_t v, int32_t last) {
-    return __builtin_amdgcn_update_dpp(last, v, 0x130, 0xf, 0xf, false);
 }
 
 // Reserve (jc, jm, jg) on slots [s, e) of a run list of n <= 64 runs held in registers (run

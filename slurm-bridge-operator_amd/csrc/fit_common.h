@@ -6,67 +6,10 @@
 #include <type_traits>
 
 #include "fit_device.h"
+#include "fit_key.h"   // fit_score, fit_key: SPEC §2's score and key
+#include "fit_wave.h"  // wave minima (wave_min_key, wave_min32_all), umin64 / umax64
 
 namespace fitgpu {
-
-__device__ __forceinline__ uint64_t fit_key(int32_t cf, int32_t mf, int32_t gf, int32_t av,
-                                            uint32_t mask, uint32_t pos, const JobRec& J) {
-    const int32_t dc = cf - J.cpu, dm = mf - J.mem, dg = gf - J.gpu, da = av - J.wall;
-    const bool ok = (dc | dm | dg | da) >= 0 && (mask & J.pbit);
-    const uint32_t sc = (min((uint32_t)dg, 255u) << 24) | (min((uint32_t)dc, 4095u) << 12) |
-                        min((uint32_t)dm >> 10, 4095u);
-    return ok ? (((uint64_t)sc << 32) | pos) : KEY_INF;
-}
-
-// ---- wave-wide reductions (DPP; call with a full EXEC mask) ---------------------------
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint32_t dpp_min(uint32_t v) {
-    return min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffff, (int)v, CTRL, ROWMASK,
-                                                        0xf, false));
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    v = dpp_min<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v = dpp_min<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]
-    v = dpp_min<0x124, 0xf>(v);  // row_ror:4
-    v = dpp_min<0x128, 0xf>(v);  // row_ror:8
-    v = dpp_min<0x142, 0xa>(v);  // row_bcast:15
-    v = dpp_min<0x143, 0xc>(v);  // row_bcast:31
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// min over the wave of a packed (score << 32 | position) key: 32-bit min of the scores, then of
-// the positions among the lanes holding that score (usually one lane: a readlane).
-__device__ __forceinline__ uint64_t wave_min_key(uint64_t v) {
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    const uint32_t mh = wave_min_u32(hi);
-    const uint64_t eq = __ballot(hi == mh);
-    uint32_t ml;
-    if (__popcll(eq) == 1)
-        ml = (uint32_t)__builtin_amdgcn_readlane((int)lo, __builtin_ctzll(eq));
-    else
-        ml = wave_min_u32(hi == mh ? lo : 0xffffffffu);
-    return ((uint64_t)mh << 32) | ml;
-}
-
-// wave_min_key plus the lane holding the minimum (the lowest such lane)
-__device__ __forceinline__ uint64_t wave_min_key_lane(uint64_t v, int& lane) {
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    const uint32_t mh = wave_min_u32(hi);
-    const uint64_t eq = __ballot(hi == mh);
-    uint32_t ml;
-    if (__popcll(eq) == 1) {
-        lane = __builtin_ctzll(eq);
-        ml = (uint32_t)__builtin_amdgcn_readlane((int)lo, lane);
-    } else {
-        ml = wave_min_u32(hi == mh ? lo : 0xffffffffu);
-        lane = __builtin_ctzll(__ballot(hi == mh && lo == ml));
-    }
-    return ((uint64_t)mh << 32) | ml;
-}
-
-__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a < b ? b : a; }
 
 // sorted ascending insert of x (< KEY_INF) into key[0..K) dropping the largest (static indices
 // only).  Entry i becomes key[i-1] if x < key[i-1], x if key[i-1] <= x < key[i], else key[i]:
@@ -138,8 +81,7 @@ __device__ __forceinline__ void scan_row(const NodeRec& r, int x, const JobRec& 
     const int32_t da = r.avail - J.wall;
     const int32_t dp = (int32_t)((r.mask & J.pbit) - 1u);  // -1: not a member (or idle lane)
     const int32_t bad = dc | dm | dg | da | dp;
-    const uint32_t sc = (min((uint32_t)dg, 255u) << 24) | (min((uint32_t)dc, 4095u) << 12) |
-                        min((uint32_t)dm >> 10, 4095u);
+    const uint32_t sc = fit_score(dc, dm, dg);
     if (bad >= 0 && sc <= lim) {
         topk_insert(key, ((uint64_t)sc << 32) | (uint32_t)x);
         const uint64_t last = key[K - 1];
@@ -454,25 +396,10 @@ __device__ unsigned long long g_stamps[64][10];  // [8], [9]: STAMP_CNT2 counter
 // lane's dirty entry i (-1: not picked).  kth = the K-th key (INF when fewer
 // than K exist).  Returns how many were found.  Each lane sorts its entries once; then every
 // extraction is a wave minimum of the lane heads — the 32-bit minimum of the scores, then of the
-// positions among the lanes holding it, each as four fused DPP minima and the permlane16 / 32 swaps
-// of gfx950 (in every lane, no readlane, no branch) — and the lane that held it pops its head.
+// positions among the lanes holding it (wave_min32_all) — and the lane that held it pops its head.
 // Round 5: the previous form (a 64-bit wave minimum over every entry, with a readlane and a tie
 // branch, and a pass clearing the taken key) cost ≈ 500 cycles per extraction at C4
 // (profiles/r05q_c4_stamps.txt).
-#define SK_DPP_MIN(v, CTL) asm volatile("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 " CTL : "+v"(v))
-__device__ __forceinline__ uint32_t sk_wave_min32_all(uint32_t v) {
-    SK_DPP_MIN(v, "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
-    SK_DPP_MIN(v, "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
-    SK_DPP_MIN(v, "row_half_mirror row_mask:0xf bank_mask:0xf");
-    SK_DPP_MIN(v, "row_mirror row_mask:0xf bank_mask:0xf");  // every lane: its row's minimum
-    {
-        const auto p = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        v = min((uint32_t)p[0], (uint32_t)p[1]);
-    }
-    const auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return min((uint32_t)p[0], (uint32_t)p[1]);
-}
-#undef SK_DPP_MIN
 template <int EPL>
 __device__ __forceinline__ int select_k(int K, const uint64_t (&kr)[EPL], const bool (&cl)[EPL],
                                         const uint64_t (&dk)[UPL], uint64_t (&sel)[FIT_KMAX],
@@ -505,8 +432,8 @@ __device__ __forceinline__ int select_k(int K, const uint64_t (&kr)[EPL], const 
     for (int s = 0; s < FIT_KMAX; ++s) {
         if (s >= K) break;  // uniform
         const uint32_t hh = (uint32_t)(q[0] >> 32), ll = (uint32_t)q[0];
-        const uint32_t mh = sk_wave_min32_all(hh);
-        const uint32_t ml = sk_wave_min32_all(hh == mh ? ll : 0xffffffffu);
+        const uint32_t mh = wave_min32_all(hh);
+        const uint32_t ml = wave_min32_all(hh == mh ? ll : 0xffffffffu);
         const uint64_t b = ((uint64_t)mh << 32) | ml;
         if (b == KEY_INF) break;  // uniform: fewer than K keys
         bool d = false;
@@ -648,9 +575,7 @@ __device__ __forceinline__ bool dirty_topk(int K, int nd, uint64_t m0, uint64_t 
                 const int32_t dg = ugpu[i] - jg, da = uav[i] - jw;                              \
                 const bool ok = (dc | dmm | dg | da) >= 0 && (umask[i] & jp) &&                 \
                                 i * 64 + lane < nu;                                             \
-                const uint32_t sc = (min((uint32_t)dg, 255u) << 24) |                           \
-                                    (min((uint32_t)dc, 4095u) << 12) |                          \
-                                    min((uint32_t)dmm >> 10, 4095u);                            \
+                const uint32_t sc = fit_score(dc, dmm, dg);                                     \
                 dk[i] = ok ? (((uint64_t)sc << 32) | upos[i]) : KEY_INF;                        \
                 dm = umin64(dm, dk[i]);                                                         \
             }                                                                                   \

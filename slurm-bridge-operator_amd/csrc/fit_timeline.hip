@@ -43,14 +43,6 @@ __device__ unsigned long long g_tlst[64][12];
 #define TL_ACC(i, a, b)
 #endif
 
-// a VGPR zero the compiler cannot see through: keeps wave-uniform loads on the vector path
-// (vmcnt, in order, so a load issued for the next item is not waited for with this one's)
-__device__ __forceinline__ int tl_vzero() {
-    int z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-
 // Earliest start of a d-slot window whose every run holds (jc, jm, jg), and its key, for `live`
 // lanes walking their node's runs [0, cnt) (any address space; the loop is wave-uniform).
 __device__ __forceinline__ uint64_t tl_eval(const Seg* sg, int cnt, bool live, int32_t jc,
@@ -277,7 +269,7 @@ __device__ __forceinline__ bool scan_tile_tl(
             tl_scan_node<true, K>(h, x, J, H, slab, key, batches, sr + (x - a) * TL_STAGE_RUNS);
         }
     } else if (n0 < n1) {
-        const int z = tl_vzero();
+        const int z = opaque_zero();
         TlHdr h0 = hdr[n0 + z], h1 = hdr[min(n0 + 1, n1 - 1) + z];
         for (int x = n0; x < n1; x += 2) {
             longn += h0.cnt > TL_HEAD;
@@ -395,25 +387,6 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_scan_tl(
 }
 
 // --------------------------------------------------------------------------- k_commit_tl
-// Three independent inclusive min-scans (a run list's cpu / mem / gpu columns), interleaved so
-// that each fused v_min_i32_dpp reads a VGPR written two instructions earlier (the DPP hazard's
-// two wait states, cdna_hip_programming.md) — 18 VALU and one s_nop.  A lane whose DPP source does
-// not exist (row_shr at a row's start) or whose row the row_mask leaves out keeps its value
-// (bound_ctrl not set), i.e. min(v, TL_BIG) = v.
-__device__ __forceinline__ void wave_scan_min3(int32_t& a, int32_t& b, int32_t& c) {
-#define TL_L3(CTL) "v_min_i32_dpp %0, %0, %0 " CTL "\n\tv_min_i32_dpp %1, %1, %1 " CTL \
-                   "\n\tv_min_i32_dpp %2, %2, %2 " CTL "\n\t"
-    asm volatile("s_nop 1\n\t"
-                 TL_L3("row_shr:1 row_mask:0xf bank_mask:0xf")
-                 TL_L3("row_shr:2 row_mask:0xf bank_mask:0xf")
-                 TL_L3("row_shr:4 row_mask:0xf bank_mask:0xf")
-                 TL_L3("row_shr:8 row_mask:0xf bank_mask:0xf")
-                 TL_L3("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 TL_L3("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 : "+v"(a), "+v"(b), "+v"(c));
-#undef TL_L3
-}
-
 // Prefix minima of an LDS run list (<= 64 runs): PM[i] = min over runs [0, i] per column.
 // With them, "fits from slot 0 for d slots" and that window's minimum are one search over the
 // run ends — the dirty-node fast path.
@@ -540,7 +513,7 @@ __device__ __forceinline__ CommitResult commit_tl_window(
         off[k] = has[k] ? g * rank_stride + P.cand_off + (e - g * per_rank) : P.cand_off;
     }
     const uint32_t nb = (uint32_t)P.nb;
-    const int z = tl_vzero();
+    const int z = opaque_zero();
     int nu = 0, placed = 0, stop = 0, t = 0;
     // this lane's dirty node (lane < nu): position, mask, id, run count, column ceilings, and
     // whether its list lives in the global slab instead of LDS

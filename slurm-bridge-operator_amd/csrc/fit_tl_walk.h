@@ -1,19 +1,19 @@
 // fit_tl_walk.h — the exact earliest-start walk over one node's run list (SPEC §2b; DESIGN.md
-// §3.8), shared by the backfill engines (fit_timeline.hip) and the read-only query (fit_when.hip).
-// Moved here verbatim from fit_timeline.hip: every function is __forceinline__, so the engines'
-// generated code is what it was.
+// §3.8) and its key, shared by the backfill engines (fit_timeline.hip), the multi-node backfill
+// (fit_place_tl_k.hip) and the read-only queries (fit_when.hip, fit_when_k.hip).  Every function is
+// __forceinline__.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "fit_device.h"
+#include "fit_key.h"  // fit_score: the score field of tl_key
 
 namespace fitgpu {
 
 __device__ __forceinline__ uint64_t tl_key(int32_t s, int32_t mc, int32_t mm, int32_t mg,
                                            int32_t jc, int32_t jm, int32_t jg, uint32_t pos) {
-    const uint32_t sc = (min((uint32_t)(mg - jg), 255u) << 24) |
-                        (min((uint32_t)(mc - jc), 4095u) << 12) |
-                        min((uint32_t)(mm - jm) >> 10, 4095u);
+    const int32_t dg = mg - jg, dc = mc - jc, dm = mm - jm;  // (g, c, m: the order tl_key always had)
+    const uint32_t sc = fit_score(dc, dm, dg);
     return ((uint64_t)(uint32_t)s << 54) | ((uint64_t)sc << TL_POS_BITS) | pos;
 }
 
