@@ -349,6 +349,17 @@ struct fit_ctx : CtxHandles {
     DBuf<int64_t> free_acc;
     DBuf<fit_free> free_rows;
     double free_ms = -1;
+    // fit_load_victims / fit_preempt: the host entry point's staged CSR, the
+    // check's flag word, the victims in row order (voff: nn + 1 offsets; vent: priority and saturated
+    // prefix sums), then the query's rows, its staged priorities and the per-slice key partials
+    DBuf<int32_t> vs_off, vs_prio, vs_cpu, vs_mem, vs_gpu, vic_bad, voff;
+    HBuf<int32_t> h_vic_bad;
+    DBuf<VicEnt> vent;
+    bool have_vic = false;
+    QueryBufs<fit_evict> pe;
+    DBuf<int32_t> pe_prio;
+    HBuf<int32_t> h_pe_prio;
+    DBuf<uint4> pe_part;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -375,6 +386,7 @@ struct fit_ctx : CtxHandles {
     DBuf<uint32_t> col_mask;
     DBuf<int32_t> rb_cpu, rb_mem, rb_gpu;  // fit_read_nodes scratch (col_* stay the loaded table)
     std::vector<uint32_t> h_mask;
+    std::vector<int32_t> h_perm;  // row position -> caller's node id (fit_load_victims orders its lists by it)
     bool have_nodes = false;
     int64_t loads = 0;        // successful node-table loads (admit.cpp notices a direct load)
 
@@ -481,6 +493,8 @@ int load_nodes_common(fit_ctx* c, int32_t n) {
     int rc = build_ptab(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));
+    perm.resize(c->nn);
+    c->h_perm.swap(perm);
     c->n = n;
     c->have_nodes = true;
     c->have_tl = false;  // a timeline belongs to the node table it was built from
@@ -1447,6 +1461,69 @@ int room_impl(fit_ctx* c, int32_t J, const JobCols& d, struct fit_room* out, int
         });
 }
 
+// --------------------------------------------------------------------------- fit_preempt
+// fit_room's sequence with the walk over each row's victims — classify, (a
+// long queue: the jobs in component order), then per chunk of PRE_CHUNK positions walk and finalise.
+// Bounded launches on the context's stream, nothing waits on another workgroup.  Device pointers;
+// *bad and the rows are valid once the caller has drained the stream.
+static_assert(PRE_FITS == FIT_PRE_FITS && PRE_PARTITION == FIT_PRE_PARTITION && PRE_LIMIT_TIME == FIT_PRE_LIMIT_TIME &&
+                  PRE_LIMIT_CPUS == FIT_PRE_LIMIT_CPUS && PRE_LIMIT_MEM == FIT_PRE_LIMIT_MEM &&
+                  PRE_NO_NODES == FIT_PRE_NO_NODES && PRE_EVICT == FIT_PRE_EVICT && PRE_NONE == FIT_PRE_NONE,
+              "fit_device.h and fitgpu.h disagree");
+static_assert(FIT_PRE_PARTITION == FIT_WHY_PARTITION && FIT_PRE_LIMIT_TIME == FIT_WHY_LIMIT_TIME &&
+                  FIT_PRE_LIMIT_CPUS == FIT_WHY_LIMIT_CPUS && FIT_PRE_LIMIT_MEM == FIT_WHY_LIMIT_MEM &&
+                  FIT_PRE_NO_NODES == FIT_WHY_NO_NODES,
+              "codes 1..5 of FIT_PRE_* are FIT_WHY_*'s");
+static_assert(sizeof(fit_evict) == 32 && offsetof(fit_evict, code) == 0 && offsetof(fit_evict, node) == 4 &&
+                  offsetof(fit_evict, victims) == 8 && offsetof(fit_evict, top_prio) == 12 &&
+                  offsetof(fit_evict, members) == 16 && offsetof(fit_evict, fit) == 20 &&
+                  offsetof(fit_evict, able) == 24 && offsetof(fit_evict, outranked) == 28,
+              "fit_evict is 32 bytes: code, node, victims, top_prio, then the four counters");
+
+int preempt_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio, fit_evict* out, int32_t* bad) {
+    const int S = preempt_slices(J, c->cls_maxn, c->cus);
+    if (c->pe_part.ensure(preempt_partials(J, S))) return FIT_E_OOM;
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_preempt_classify(c->st, c->d_ptab.p, c->np, c->ncomp, d.cpu, d.mem, d.gpu, d.wall, d.part, J,
+                                           out, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_preempt(c->st, c->rec.p, c->voff.p, c->vent.p, ec, d.cpu, d.mem, d.gpu, d.wall, d.part, prio,
+                                  J, c->jcomp.p, jl, live, S, c->pe_part.p, out);
+        });
+}
+
+// fit_load_victims / fit_load_victims_device behind their checks: the row-ordered offsets from the
+// caller's (h_off: host copy, nullptr = every list empty), then the entries from the device CSR.
+// The victims loaded before are replaced from the first write on.
+int load_victims_impl(fit_ctx* c, const int32_t* h_off, const int32_t* off, const int32_t* prio, const int32_t* cpu,
+                      const int32_t* mem, const int32_t* gpu) {
+    std::vector<int32_t> hv((size_t)c->nn + 1, 0);
+    if (h_off)
+        for (int32_t i = 0; i < c->nn; ++i) {
+            const int32_t x = c->h_perm[i];
+            hv[i + 1] = hv[i] + (h_off[x + 1] - h_off[x]);
+        }
+    c->have_vic = false;
+    if (c->voff.ensure(hv.size()) || c->vent.ensure(std::max<int32_t>(hv[c->nn], 1))) return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->voff.p, hv.data(), sizeof(int32_t) * hv.size(), hipMemcpyHostToDevice, c->st));
+    if (hv[c->nn] > 0)
+        HIP_TRY(launch_vic_build(c->st, off, prio, cpu, mem, gpu, c->perm.p, c->nn, c->voff.p, c->vent.p));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    c->have_vic = true;
+    return 0;
+}
+
+int check_victims_state(fit_ctx* c) {
+    if (!c) return fail(FIT_E_INVAL, "null ctx");
+    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
+    if (c->collective())
+        return fail(FIT_E_STATE, "fit_load_victims on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
+    return 0;
+}
+
 // --------------------------------------------------------------------------- fit_when_k
 // classify the batch, (more than a group of jobs on several components: the
 // jobs in component order), then per chunk of WHENK_CHUNK jobs count (difference arrays), pick the
@@ -2051,6 +2128,7 @@ static int load_node_cols(fit_ctx* c, int32_t n, const int32_t* cpu, const int32
     // the columns are overwritten below: until the load succeeds there is no valid node table
     // (a failed load must not leave new offsets paired with old node rows)
     c->have_nodes = c->have_tl = false;
+    c->have_vic = false;  // the victims are lists by node id, and the ids change
     HIP_TRY(hipSetDevice(c->device));
     if (alloc_cols(c, n)) return FIT_E_OOM;
     const size_t b = sizeof(int32_t) * n;
@@ -2276,6 +2354,109 @@ int fit_room_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->rm.ms < 0) return fail(FIT_E_STATE, "no fit_room_device yet");
     *ms = c->rm.ms;
+    return 0;
+}
+
+int fit_load_victims(fit_ctx* c, const int32_t* vic_off, const int32_t* vic_prio, const int32_t* vic_cpu,
+                     const int32_t* vic_mem, const int32_t* vic_gpu) {
+    const int rc = check_victims_state(c);
+    if (rc) return rc;
+    int64_t nv = 0;
+    if (vic_off) {  // everything is judged before anything is written: a bad list leaves the loaded victims
+        if (vic_off[0] != 0) return fail(FIT_E_INVAL, "vic_off[0] must be 0");
+        for (int32_t x = 0; x < c->n; ++x)
+            if (vic_off[x + 1] < vic_off[x]) return fail(FIT_E_INVAL, "vic_off decreases at %d", x);
+        nv = vic_off[c->n];
+        if (nv > 0 && (!vic_prio || !vic_cpu || !vic_mem || !vic_gpu)) return fail(FIT_E_INVAL, "null victim arrays");
+        for (int32_t x = 0; x < c->n; ++x)
+            for (int32_t k = vic_off[x]; k < vic_off[x + 1]; ++k) {
+                if (vic_cpu[k] < 0 || vic_mem[k] < 0 || vic_gpu[k] < 0)
+                    return fail(FIT_E_INVAL, "victim %d of node %d holds a negative amount", k - vic_off[x], x);
+                if (k > vic_off[x] && vic_prio[k] < vic_prio[k - 1])
+                    return fail(FIT_E_INVAL, "victims of node %d are not in eviction order (priority decreases at %d)",
+                                x, k - vic_off[x]);
+            }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (nv > 0) {
+        const size_t b = sizeof(int32_t) * nv, bo = sizeof(int32_t) * ((size_t)c->n + 1);
+        if (c->vs_off.ensure((size_t)c->n + 1) || c->vs_prio.ensure(nv) || c->vs_cpu.ensure(nv) ||
+            c->vs_mem.ensure(nv) || c->vs_gpu.ensure(nv))
+            return FIT_E_OOM;
+        HIP_TRY(hipMemcpyAsync(c->vs_off.p, vic_off, bo, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_prio.p, vic_prio, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_cpu.p, vic_cpu, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_mem.p, vic_mem, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_gpu.p, vic_gpu, b, hipMemcpyHostToDevice, c->st));
+    }
+    return load_victims_impl(c, nv > 0 ? vic_off : nullptr, c->vs_off.p, c->vs_prio.p, c->vs_cpu.p, c->vs_mem.p,
+                             c->vs_gpu.p);
+}
+
+int fit_load_victims_device(fit_ctx* c, const int32_t* vic_off, int64_t n_vic, const int32_t* vic_prio,
+                            const int32_t* vic_cpu, const int32_t* vic_mem, const int32_t* vic_gpu) {
+    const int rc = check_victims_state(c);
+    if (rc) return rc;
+    if (n_vic < 0 || n_vic > INT32_MAX || (n_vic > 0 && (!vic_off || !vic_prio || !vic_cpu || !vic_mem || !vic_gpu)))
+        return fail(FIT_E_INVAL, "bad victim arrays");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!vic_off) return load_victims_impl(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    // the lists are judged by a kernel, the offsets come to the host for the row order; the loaded
+    // victims stay untouched until the verdict is in
+    if (c->vic_bad.ensure(1) || c->h_vic_bad.ensure(1)) return FIT_E_OOM;
+    std::vector<int32_t> h_off((size_t)c->n + 1);
+    HIP_TRY(hipMemsetAsync(c->vic_bad.p, 0, sizeof(int32_t), c->st));
+    HIP_TRY(launch_vic_check(c->st, vic_off, c->n, n_vic, vic_prio, vic_cpu, vic_mem, vic_gpu, c->vic_bad.p));
+    HIP_TRY(hipMemcpyAsync(c->h_vic_bad.p, c->vic_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(h_off.data(), vic_off, sizeof(int32_t) * h_off.size(), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->h_vic_bad.p[0])
+        return fail(FIT_E_INVAL, "victims: vic_off must start at 0, not decrease and end at n_vic; amounts >= 0; "
+                                 "priorities non-decreasing inside a node");
+    return load_victims_impl(c, n_vic > 0 ? h_off.data() : nullptr, vic_off, vic_prio, vic_cpu, vic_mem, vic_gpu);
+}
+
+// fit_preempt / fit_preempt_device: fit_room's tests, then the victims
+static int check_preempt_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays) {
+    const int rc = check_job_args(c, j, arrays, "fit_preempt", -1);
+    if (rc) return rc;
+    if (!c->have_vic) return fail(FIT_E_STATE, "fit_load_victims not called");
+    return 0;
+}
+
+int fit_preempt(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* wall,
+                const uint16_t* part, const int32_t* prio, fit_evict* out) {
+    const int rc = check_preempt_args(c, j, {cpu, mem, gpu, wall, part, prio, out});
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the priorities ride beside the packed columns: pinned, one copy on the context's stream
+    if (c->pe_prio.ensure(j) || c->h_pe_prio.ensure(j)) return FIT_E_OOM;
+    memcpy(c->h_pe_prio.p, prio, sizeof(int32_t) * j);
+    HIP_TRY(hipMemcpyAsync(c->pe_prio.p, c->h_pe_prio.p, sizeof(int32_t) * j, hipMemcpyHostToDevice, c->st));
+    return query_host(
+        c, c->pe, j, cpu, mem, gpu, wall, part, nullptr, out,
+        [](fit_ctx* x, int32_t n, const JobCols& d, fit_evict* rows, int32_t* bad) {
+            return preempt_impl(x, n, d, x->pe_prio.p, rows, bad);
+        },
+        bad_room_job);
+}
+
+int fit_preempt_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* part, const int32_t* prio, fit_evict* out) {
+    const int rc = check_preempt_args(c, j, {cpu, mem, gpu, wall, part, prio, out});
+    if (rc || j == 0) return rc;
+    return query_device(
+        c, c->pe, j, {cpu, mem, gpu, wall, part, nullptr}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict* rows, int32_t* bad) {
+            return preempt_impl(x, n, d, prio, rows, bad);
+        },
+        bad_room_job);
+}
+
+int fit_preempt_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->pe.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_device yet");
+    *ms = c->pe.ms;
     return 0;
 }
 

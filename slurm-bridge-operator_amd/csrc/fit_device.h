@@ -339,6 +339,43 @@ hipError_t launch_room(hipStream_t st, const NodeRec* rec, const ExplainComps& C
                        const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                        int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* out);
 
+// ---- fit_load_victims / fit_preempt (fit_preempt.hip) -------------------
+// The codes of include/fitgpu.h FIT_PRE_* (engine.cpp asserts they agree); 5 is EX_NO_NODES.
+enum PreemptCode : int32_t {
+    PRE_FITS = LIM_NONE,
+    PRE_PARTITION = LIM_PARTITION,
+    PRE_LIMIT_TIME = LIM_LIMIT_TIME,
+    PRE_LIMIT_CPUS = LIM_LIMIT_CPUS,
+    PRE_LIMIT_MEM = LIM_LIMIT_MEM,
+    PRE_NO_NODES = 5,
+    PRE_EVICT = 6,
+    PRE_NONE = 7,
+};
+// One victim of a row, 16 B (one scalar s_load_dwordx4): its priority and the inclusive prefix sums
+// of the row's amounts up to it, saturated at INT32_MAX
+struct alignas(16) VicEnt {
+    int32_t prio, cpu, mem, gpu;
+};
+constexpr int PRE_CHUNK = 16384;  // job positions per walk / final pair: the partials' bound
+// the caller's CSR on the device: *bad |= 1 unless the offsets start at 0, do not decrease and end at
+// nvic, the amounts are >= 0 and the priorities do not decrease inside a node
+hipError_t launch_vic_check(hipStream_t st, const int32_t* off, int32_t n, int64_t nvic, const int32_t* prio,
+                            const int32_t* cpu, const int32_t* mem, const int32_t* gpu, int32_t* bad);
+// the checked CSR into row order: voff (nn + 1 row offsets, the caller's lists permuted) -> vent
+hipError_t launch_vic_build(hipStream_t st, const int32_t* off, const int32_t* prio, const int32_t* cpu,
+                            const int32_t* mem, const int32_t* gpu, const int32_t* perm, int32_t nn,
+                            const int32_t* voff, VicEnt* vent);
+hipError_t launch_preempt_classify(hipStream_t st, const int32_t* ptab, int32_t np, int ncomp, const int32_t* jcpu,
+                                   const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                   const uint16_t* jpart, int32_t nj, void* out, int8_t* jcomp, int32_t* bad);
+int preempt_slices(int32_t nj, int32_t maxn, int cus);
+size_t preempt_partials(int32_t nj, int slices);  // 16-byte words of `part`
+hipError_t launch_preempt(hipStream_t st, const NodeRec* rec, const int32_t* voff, const VicEnt* vent,
+                          const ExplainComps& C, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                          const int32_t* jwall, const uint16_t* jpart, const int32_t* jprio, int32_t nj,
+                          const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* part,
+                          void* out);
+
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {
     TRIP_NONE = 0,

@@ -1053,6 +1053,40 @@ int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_evict row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
+// with the same numbers and take its sentences.  No device, no context.
+int fit_preempt_message(const fit_evict* r, char* buf, int32_t buflen) {
+    if (!r || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    switch (r->code) {
+        case FIT_PRE_PARTITION:
+        case FIT_PRE_LIMIT_TIME:
+        case FIT_PRE_LIMIT_CPUS:
+        case FIT_PRE_LIMIT_MEM:
+        case FIT_PRE_NO_NODES: {
+            fit_why w;
+            memset(&w, 0, sizeof w);
+            w.code = r->code;
+            return fit_why_message(&w, buf, buflen);
+        }
+        case FIT_PRE_FITS: s = std::to_string(r->fit) + "/" + std::to_string(r->members) + " nodes fit now"; break;
+        case FIT_PRE_EVICT:
+            s = "fits node " + std::to_string(r->node) + " after evicting " + std::to_string(r->victims) +
+                " lower-priority jobs (highest priority " + std::to_string(r->top_prio) + "): " +
+                std::to_string(r->able) + "/" + std::to_string(r->members) + " nodes can be freed";
+            break;
+        case FIT_PRE_NONE:
+            s = "no node can be freed on any of " + std::to_string(r->members) + " nodes";
+            if (r->outranked != 0)
+                s += ": " + std::to_string(r->outranked) + " held by jobs of equal or higher priority";
+            break;
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 // A fit_free row as one line; the texts are fixed in include/fitgpu.h.  No device, no context.
 int fit_free_message(const fit_free* r, char* buf, int32_t buflen) {
     if (!r || !buf || buflen < 1) return FIT_E_INVAL;

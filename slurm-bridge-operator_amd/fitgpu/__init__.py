@@ -37,7 +37,9 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta, FitEtaK, FIT_MAX_K,
                    FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
                    FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom,
-                   FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED, FitFree)
+                   FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED, FitFree,
+                   FIT_PRE_EVICT, FIT_PRE_FITS, FIT_PRE_LIMIT_CPUS, FIT_PRE_LIMIT_MEM, FIT_PRE_LIMIT_TIME,
+                   FIT_PRE_NO_NODES, FIT_PRE_NONE, FIT_PRE_PARTITION, FitEvict)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -56,6 +58,8 @@ __all__ = [
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
     "FIT_HOLD_HELD", "FIT_HOLD_REFUSED", "FIT_HOLD_SKIPPED",
     "free_message", "FREE_DTYPE", "FitFree",
+    "preempt_message", "EVICT_DTYPE", "FitEvict", "FIT_PRE_FITS", "FIT_PRE_PARTITION", "FIT_PRE_LIMIT_TIME",
+    "FIT_PRE_LIMIT_CPUS", "FIT_PRE_LIMIT_MEM", "FIT_PRE_NO_NODES", "FIT_PRE_EVICT", "FIT_PRE_NONE",
 ]
 
 
@@ -417,6 +421,21 @@ def free_message(row) -> str:
     r = FitFree(*(int(get(n)) for n, _ in FitFree._fields_))
     buf = C.create_string_buffer(256)
     n = check(lib().fit_free_message(C.byref(r), buf, len(buf)), "fit_free_message")
+    return buf.raw[:n].decode()
+
+
+# ---------------------------------------------------------------------------------- preempt
+# one fit_evict row (include/fitgpu.h), 32 bytes of int32: what Engine.preempt returns
+EVICT_DTYPE = np.dtype([(n, np.int32) for n, _ in FitEvict._fields_])
+
+
+def preempt_message(row) -> str:
+    """A fit_evict row (an element of a preempt() result, or any mapping / object with its fields)
+    as one line of text (fit_preempt_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    r = FitEvict(*(int(get(n)) for n, _ in FitEvict._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_preempt_message(C.byref(r), buf, len(buf)), "fit_preempt_message")
     return buf.raw[:n].decode()
 
 
@@ -833,6 +852,62 @@ class Engine:
             return 0.0
         ms = C.c_double()
         check(lib().fit_room_ms(self._h, C.byref(ms)), "fit_room_ms")
+        return ms.value
+
+    # ---- which running jobs to evict so that a pending job fits ---------------
+    def load_victims(self, victims):
+        """The preemptible running jobs per node (fit_load_victims): `victims` has off (n + 1), prio,
+        cpu, mem, gpu — a CSR by node id, each node's entries in eviction order (priority
+        non-decreasing) — or is None: every list empty.  After load_nodes, which drops them."""
+        if victims is None:
+            check(lib().fit_load_victims(self._h, None, None, None, None, None), "fit_load_victims")
+            return
+        cols = [np.ascontiguousarray(getattr(victims, f), np.int32) for f in ("off", "prio", "cpu", "mem", "gpu")]
+        if len(cols[0]) != self.n + 1 or any(len(c) != len(cols[1]) for c in cols[2:]) or (
+                len(cols[0]) and int(cols[0].max()) > len(cols[1])):
+            raise ValueError("victims: off must have n + 1 entries that index equally long columns")
+        check(lib().fit_load_victims(self._h, *[_ptr(c) if len(c) else None for c in cols]), "fit_load_victims")
+
+    def load_victims_device(self, off, prio, cpu, mem, gpu):
+        """torch int32 tensors on this GPU (off has n + 1 entries, the others off[n]); off None: every
+        list empty.  The lists are validated by a kernel."""
+        if off is None:
+            check(lib().fit_load_victims_device(self._h, None, 0, None, None, None, None), "fit_load_victims_device")
+            return
+        check(lib().fit_load_victims_device(self._h, _ptr(off), int(prio.numel()),
+                                            *[_ptr(t) if t.numel() else None for t in (prio, cpu, mem, gpu)]),
+              "fit_load_victims_device")
+
+    def preempt(self, jobs, prio):
+        """Every job judged alone against the current node table and the loaded victims
+        (fit_preempt): a structured array of EVICT_DTYPE rows (code, node, victims, top_prio, members,
+        fit, able, outranked).  prio: the jobs' priorities (int32).  Changes nothing; jobs.nodes_k
+        plays no part (each job takes one node)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        prio = np.ascontiguousarray(prio, np.int32)
+        if len(prio) != len(part):
+            raise ValueError("prio must have one entry per job")
+        out = np.zeros(len(part), EVICT_DTYPE)
+        check(lib().fit_preempt(self._h, len(part), *[_ptr(c) for c in cols], _ptr(part), _ptr(prio), _ptr(out)),
+              "fit_preempt")
+        return out
+
+    def preempt_device(self, cpu, mem, gpu, wall, part, prio, out):
+        """All arguments torch tensors resident on this GPU; writes out (J rows of 8 int32, the fields
+        of EVICT_DTYPE in order).  Returns the device time of its launches in ms (HIP events on the
+        context's stream, fit_preempt_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_preempt_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                       _ptr(prio), _ptr(out)), "fit_preempt_device")
+        if j == 0:
+            return 0.0
+        return self.preempt_ms()
+
+    def preempt_ms(self):
+        """Device time in ms of the last successful preempt_device (fit_preempt_ms)."""
+        ms = C.c_double()
+        check(lib().fit_preempt_ms(self._h, C.byref(ms)), "fit_preempt_ms")
         return ms.value
 
     # ---- free capacity per partition and slot (DESIGN.md §2k) --------------------------------

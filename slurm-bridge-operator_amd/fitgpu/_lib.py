@@ -49,6 +49,8 @@ EXPORTS = [
     "fit_advance_tl", "fit_advance_tl_device", "fit_advance_tl_ms",
     "fit_hold_tl", "fit_hold_tl_device", "fit_hold_tl_ms",
     "fit_free_tl", "fit_free_tl_device", "fit_free_tl_ms", "fit_free_message",
+    "fit_load_victims", "fit_load_victims_device", "fit_preempt", "fit_preempt_device", "fit_preempt_ms",
+    "fit_preempt_message",
 ]
 
 
@@ -133,6 +135,15 @@ class FitRoom(C.Structure):
                 ("by_mem", C.c_int32)]
 
 
+# fit_evict.code (include/fitgpu.h): 1-5 are FIT_WHY_*'s; precedence 1, 2, 3, 4, 5, 0, 6, 7
+FIT_PRE_FITS, FIT_PRE_PARTITION, FIT_PRE_LIMIT_TIME, FIT_PRE_LIMIT_CPUS = 0, 1, 2, 3
+FIT_PRE_LIMIT_MEM, FIT_PRE_NO_NODES, FIT_PRE_EVICT, FIT_PRE_NONE = 4, 5, 6, 7
+
+
+class FitEvict(C.Structure):  # fit_evict: one row of fit_preempt, 32 bytes
+    _fields_ = [(n, C.c_int32) for n in ("code", "node", "victims", "top_prio", "members", "fit", "able", "outranked")]
+
+
 class FitFree(C.Structure):  # fit_free: one (partition, slot) row of fit_free_tl, 40 bytes
     _fields_ = [("cpu", C.c_int64), ("mem", C.c_int64), ("gpu", C.c_int64), ("nodes", C.c_int32),
                 ("max_cpu", C.c_int32), ("max_mem", C.c_int32), ("max_gpu", C.c_int32)]
@@ -215,6 +226,12 @@ def lib() -> C.CDLL:
         L.fit_room_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_room_message.argtypes = [C.POINTER(FitRoom), C.c_char_p, i32]
         L.fit_admitter_room.argtypes = [P, C.POINTER(FitAdmitReq), i32, P]
+        L.fit_load_victims.argtypes = [P, P, P, P, P, P]
+        L.fit_load_victims_device.argtypes = [P, P, i64, P, P, P, P]
+        for name in ("fit_preempt", "fit_preempt_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P]
+        L.fit_preempt_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_preempt_message.argtypes = [C.POINTER(FitEvict), C.c_char_p, i32]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

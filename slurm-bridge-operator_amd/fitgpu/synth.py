@@ -284,6 +284,66 @@ def make_c5(nodes: int | None = None, jobs: int | None = None, shard: int = 0):
             gen_jobs(seed, j, p, mn, start=shard * j), gen_partitions(seed, p))
 
 
+# ---- preemptible running jobs (fit_load_victims) ------------------------------
+S_VEMPTY, S_VCPU, S_VMEM, S_VGPU, S_VPRIO, S_JPRIO = range(40, 46)
+VIC_CPUS = np.array([2, 4, 8, 16, 32], dtype=np.int64)
+VIC_MEMMUL = np.array([1024, 2048, 4096], dtype=np.int64)
+VIC_GPUS = np.array([0, 0, 0, 1, 2], dtype=np.int64)
+VIC_PRIO = np.array([-5, 0, 10, 10, 100, 1000], dtype=np.int64)
+JOB_PRIO = np.array([0, 10, 11, 100, 1001], dtype=np.int64)
+VIC_SLOTS = 48     # victims a node takes at most; the last takes whatever cpus are left
+VIC_EMPTY_PM = 20  # nodes per thousand that stay as they are, without a victim
+
+
+@dataclass
+class Victims:
+    """The preemptible running jobs per node, CSR by node id: node x's victims are
+    [off[x], off[x+1]) in eviction order (prio non-decreasing), each holding (cpu, mem, gpu) there."""
+    off: np.ndarray   # int32 [n + 1]
+    prio: np.ndarray  # int32 [V]
+    cpu: np.ndarray   # int32 [V]
+    mem: np.ndarray   # int32 [V], MiB
+    gpu: np.ndarray   # int32 [V]
+
+
+def pack_victims(seed: int, nodes: Nodes, cpus=VIC_CPUS, empty_pm: int = VIC_EMPTY_PM) -> tuple[Nodes, Victims]:
+    """A packed cluster: every node but about empty_pm per thousand takes victims — running jobs of
+    `cpus` cpus, each with memory and GPUs as far as the node has them — until it has no free cpu
+    left.  Returns the packed node table (the free columns lowered by what the victims hold;
+    avail_min and part_mask as they were) and the victims, priorities from VIC_PRIO, sorted per node.
+    A node with a negative free column takes none."""
+    n, K = nodes.n, VIC_SLOTS
+    i = np.arange(n, dtype=np.uint64)
+    ik = i[:, None] * np.uint64(K) + np.arange(K, dtype=np.uint64)[None, :]
+    free = [np.asarray(c, np.int64) for c in (nodes.cpu_free, nodes.mem_free, nodes.gpu_free)]
+    cpus = np.asarray(cpus, np.int64)
+    takes = (uni(rnd(seed, S_VEMPTY, i), 1000) >= empty_pm) & (free[0] >= 0) & (free[1] >= 0) & (free[2] >= 0)
+    want_c = cpus[uni(rnd(seed, S_VCPU, ik), len(cpus))]
+    want_c[:, K - 1] = np.iinfo(np.int32).max  # the last slot takes the rest
+    want = [want_c, np.minimum(want_c, 256) * VIC_MEMMUL[uni(rnd(seed, S_VMEM, ik), len(VIC_MEMMUL))],
+            VIC_GPUS[uni(rnd(seed, S_VGPU, ik), len(VIC_GPUS))]]
+    held = []
+    for f, w in zip(free, want):  # slot k holds min(want, what the slots before it left)
+        before = np.cumsum(w, axis=1) - w
+        held.append(np.clip(np.where(takes, f, 0)[:, None] - before, 0, w))
+    valid = held[0] > 0  # a prefix of the slots: the cpus run out first or with the others
+    prio = VIC_PRIO[uni(rnd(seed, S_VPRIO, ik), len(VIC_PRIO))]
+    prio = np.sort(np.where(valid, prio, np.iinfo(np.int64).max), axis=1)  # eviction order, the valid slots first
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(valid.sum(axis=1))
+    held = [np.where(valid, h, 0) for h in held]
+    packed = Nodes(*((f - h.sum(axis=1)).astype(np.int32) for f, h in zip(free, held)), nodes.avail_min.copy(),
+                   nodes.part_mask.copy())
+    return packed, Victims(off.astype(np.int32), prio[valid].astype(np.int32), held[0][valid].astype(np.int32),
+                           held[1][valid].astype(np.int32), held[2][valid].astype(np.int32))
+
+
+def gen_job_prio(seed: int, j: int, start: int = 0) -> np.ndarray:
+    """Priorities of the pending jobs [start, start + j), from JOB_PRIO."""
+    i = np.arange(start, start + j, dtype=np.uint64)
+    return JOB_PRIO[uni(rnd(seed, S_JPRIO, i), len(JOB_PRIO))].astype(np.int32)
+
+
 def make_c1():
     """C1: 8 nodes × 100 copies of manifests/samples/kubecluster.org_v1alpha1_slurmbridgejob.yaml.
 

@@ -623,6 +623,111 @@ func RoomMessage(r Room) string {
 	return string(buf[:int(n)])
 }
 
+// Victims are the preemptible running jobs of each node, CSR by node id: node x's victims are
+// [Off[x], Off[x+1]) in eviction order — Prio non-decreasing, the lowest first — each holding
+// (CPU, MemMiB, GPU) on that node (DESIGN.md §2l).
+type Victims struct {
+	Off, Prio, CPU, MemMiB, GPU []int32
+}
+
+// LoadVictims hands the engine the running jobs Preempt may evict (fit_load_victims), after
+// LoadNodes, which drops them.  An empty Off means no node has a victim.
+func (e *Engine) LoadVictims(v Victims) error {
+	if !sameLen(len(v.Prio), len(v.CPU), len(v.MemMiB), len(v.GPU)) {
+		return errLen
+	}
+	if len(v.Off) == 0 {
+		err := check(C.fit_load_victims(e.ctx, nil, nil, nil, nil, nil))
+		runtime.KeepAlive(e)
+		return err
+	}
+	if int(v.Off[len(v.Off)-1]) > len(v.Prio) {
+		return fmt.Errorf("fitgpu: Off ends at %d but there are %d victims", v.Off[len(v.Off)-1], len(v.Prio))
+	}
+	var p, c, m, g *C.int32_t
+	if len(v.Prio) > 0 {
+		p, c = (*C.int32_t)(unsafe.Pointer(&v.Prio[0])), (*C.int32_t)(unsafe.Pointer(&v.CPU[0]))
+		m, g = (*C.int32_t)(unsafe.Pointer(&v.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&v.GPU[0]))
+	}
+	err := check(C.fit_load_victims(e.ctx, (*C.int32_t)(unsafe.Pointer(&v.Off[0])), p, c, m, g))
+	runtime.KeepAlive(e)
+	return err
+}
+
+// Preempt codes (fit_evict.code, include/fitgpu.h): whether evicting running jobs makes a job fit.
+// PrePartition .. PreNoNodes are WhyPartition .. WhyNoNodes.
+const (
+	PreFits      = int32(C.FIT_PRE_FITS)
+	PrePartition = int32(C.FIT_PRE_PARTITION)
+	PreLimitTime = int32(C.FIT_PRE_LIMIT_TIME)
+	PreLimitCPUs = int32(C.FIT_PRE_LIMIT_CPUS)
+	PreLimitMem  = int32(C.FIT_PRE_LIMIT_MEM)
+	PreNoNodes   = int32(C.FIT_PRE_NO_NODES)
+	PreEvict     = int32(C.FIT_PRE_EVICT)
+	PreNone      = int32(C.FIT_PRE_NONE)
+)
+
+// Evict is one fit_evict row: the job judged alone against the current node table and the loaded
+// victims (DESIGN.md §2l).  With Code == PreEvict the caller evicts the first Victims entries of
+// Node's list, [Off[Node], Off[Node]+Victims), and the job fits Node.
+type Evict struct {
+	Code      int32 // Pre*
+	Node      int32 // the chosen node, -1 if none
+	Victims   int32 // entries of Node's list to evict, from its first; 0 unless PreEvict
+	TopPrio   int32 // priority of the last of them, the highest evicted; 0 unless PreEvict
+	Members   int32 // schedulable nodes of the job's partition
+	Fit       int32 // members the job fits now (Why.Fit)
+	Able      int32 // members a prefix of lower-priority victims frees
+	Outranked int32 // members that only jobs of equal or higher priority hold
+}
+
+func goEvict(r *C.fit_evict) Evict {
+	return Evict{Code: int32(r.code), Node: int32(r.node), Victims: int32(r.victims), TopPrio: int32(r.top_prio),
+		Members: int32(r.members), Fit: int32(r.fit), Able: int32(r.able), Outranked: int32(r.outranked)}
+}
+
+// Preempt tells for every job, judged alone, whether it fits now, and if not which node to free
+// and how many of its victims to evict (fit_preempt); it changes nothing and evicts nothing.  prio
+// has one entry per job.  NodesK is not read: each job takes one node.
+func (e *Engine) Preempt(j Jobs, prio []int32) ([]Evict, error) {
+	cnt := len(j.CPU)
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part), len(prio)) {
+		return nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil
+	}
+	rows := make([]C.fit_evict, cnt)
+	rc := C.fit_preempt(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])),
+		(*C.int32_t)(unsafe.Pointer(&prio[0])), &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Evict, cnt)
+	for i := range rows {
+		out[i] = goEvict(&rows[i])
+	}
+	return out, nil
+}
+
+// PreemptMessage is the row as one line (fit_preempt_message: "fits node 812 after evicting 2
+// lower-priority jobs (highest priority 10): 37/512 nodes can be freed"); "" for a row with an
+// unknown code.
+func PreemptMessage(r Evict) string {
+	c := C.fit_evict{code: C.int32_t(r.Code), node: C.int32_t(r.Node), victims: C.int32_t(r.Victims),
+		top_prio: C.int32_t(r.TopPrio), members: C.int32_t(r.Members), fit: C.int32_t(r.Fit),
+		able: C.int32_t(r.Able), outranked: C.int32_t(r.Outranked)}
+	buf := make([]byte, 256)
+	n := C.fit_preempt_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
 // nodes that are open there (DESIGN.md §2k).
 type Free struct {
