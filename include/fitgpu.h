@@ -722,6 +722,68 @@ int fit_preempt_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_preempt_message(const fit_evict* r, char* buf, int32_t buflen);
 
+/* ---- which victims to evict so that a MULTI-NODE job fits -------------------
+ * fit_preempt for a job that needs need = max(nodes_k, 1) distinct nodes at once, 1 <= need <= kmax
+ * <= FIT_MAX_K: Slurm's preempt/partition_prio for a wide job.  State, eligibility, L(n), S_c(v),
+ * v(n) and the counters members / fit / able / outranked are fit_preempt's, unchanged; each job is
+ * judged alone and nothing is written.  Every eligible node with some v(n) in [0, L(n)] has
+ * fit_preempt's key (top, v, score, node id); a node that fits now (v = 0) has first word 0 and sorts
+ * before every node that needs an eviction.  The keys are distinct (the node id is in them).  A job
+ * has picks when fit + able >= need: the `need` smallest keys, in key order.  So every fitting node is
+ * taken before any eviction, the highest evicted priority is the smallest possible for `need` nodes,
+ * then fewer victims win, then the better fit, then the lower node id.
+ *   out_node[q * kmax + i], i < need: the picks in key order;
+ *   out_victims[q * kmax + i]: the pick's v, 0 for a node that fits now — the caller evicts the
+ *     entries [vic_off[node], vic_off[node] + v) of each pick;
+ *   every other entry is -1 in out_node and 0 in out_victims: i >= need, and every row whose code is
+ *     neither FITS nor EVICT.
+ * The codes are FIT_PRE_* with fit_preempt's precedence (1, 2, 3, 4, 5, 0, 6, 7):
+ *   FIT_PRE_FITS   fit >= need            FIT_PRE_EVICT  fit < need <= fit + able
+ *   FIT_PRE_NONE   fit + able < need (members < need included)      FIT_PRE_NO_NODES  members == 0
+ * For codes 1-4 every field but code and need is 0.  With need == 1 the row and entry 0 of the two
+ * arrays are fit_preempt's row, field for field.  Not judged here: sparing a victim of a prefix, the
+ * timeline, the admitter; nothing is evicted. */
+typedef struct {              /* 40 bytes                                                         */
+    int32_t code;        /* FIT_PRE_*                                                             */
+    int32_t need;        /* max(nodes_k, 1); set for every code                                   */
+    int32_t evict_nodes; /* picks with v >= 1                                                     */
+    int32_t victims;     /* the sum of the picks' v (exact: distinct nodes of an int32 CSR)       */
+    int32_t top_prio;    /* the highest priority evicted: the last pick's top; 0 if evict_nodes 0 */
+    int32_t members;     /* as fit_evict                                                          */
+    int32_t fit;
+    int32_t able;
+    int32_t outranked;
+    int32_t reserved;    /* 0                                                                     */
+} fit_evict_k;
+/* Host pointers; nodes_k NULL = every job needs one node.  j == 0 returns 0 whatever the pointers
+ * are.  FIT_E_INVAL: NULL ctx / arrays, j < 0, kmax outside [1, FIT_MAX_K], a max(nodes_k, 1) above
+ * kmax, a negative cpu / mem / gpu / wall (the whole call fails).  FIT_E_STATE: as fit_preempt.
+ * Bounded launches (three per 16,384 jobs), no persistent grid: neither the per-GPU
+ * persistent-launch lock nor the watchdog. */
+int fit_preempt_k(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                  const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k /* NULL = all 1 */,
+                  const int32_t* prio, int32_t kmax, fit_evict_k* out, int32_t* out_node /* j*kmax */,
+                  int32_t* out_victims /* j*kmax */);
+/* Same with device pointers (inputs resident in HBM, the rows and the picks written in HBM). */
+int fit_preempt_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                         const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, const int32_t* prio,
+                         int32_t kmax, fit_evict_k* out, int32_t* out_node, int32_t* out_victims);
+/* Diagnostic, for measurement only (tools/preempt_k_bench.py): device time of the last successful
+ * fit_preempt_k_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
+int fit_preempt_k_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text; return value and errors as fit_room_message's (256 bytes always
+ * suffice).  The exact texts, <x> a decimal field of the row:
+ *   FIT_PRE_FITS        "fits now on <need> of <fit>/<members> nodes"
+ *   FIT_PRE_EVICT       "fits <need> nodes after evicting <victims> lower-priority jobs on
+ *                        <evict_nodes> of them (highest priority <top_prio>): <fit> fit now, <able> can
+ *                        be freed, of <members> nodes" — on one line
+ *   FIT_PRE_NONE        "needs <need> nodes: <fit> fit now, <able> can be freed, of <members> nodes:
+ *                        <outranked> held by jobs of equal or higher priority" — on one line; with
+ *                       outranked == 0 the last colon and everything after it are left out
+ *   FIT_PRE_NO_NODES / LIMIT_TIME / LIMIT_CPUS / LIMIT_MEM / PARTITION: fit_why_message's texts of
+ *                       the codes with the same numbers, verbatim */
+int fit_preempt_k_message(const fit_evict_k* r, char* buf, int32_t buflen);
+
 /* ---- free capacity of every partition at every timeline slot ---------------
  * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
  * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced

@@ -360,6 +360,12 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> pe_prio;
     HBuf<int32_t> h_pe_prio;
     DBuf<uint4> pe_part;
+    // fit_preempt_k: its rows and the picks of the host entry point (device,
+    // pinned).  It shares fit_preempt's staged priorities and key scratch: both calls run on the
+    // context's one stream and end synchronised, and each writes every word before it reads it.
+    QueryBufs<fit_evict_k> pk;
+    DBuf<int32_t> pk_node, pk_vic;
+    HBuf<int32_t> h_pk_pick;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1495,6 +1501,32 @@ int preempt_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio, f
         });
 }
 
+// --------------------------------------------------------------------------- fit_preempt_k
+// fit_preempt's sequence, the walk keeping the kmax smallest keys per (job,
+// node slice) instead of one.  Same bounded launches, slices and chunks.
+static_assert(sizeof(fit_evict_k) == 40 && offsetof(fit_evict_k, code) == 0 && offsetof(fit_evict_k, need) == 4 &&
+                  offsetof(fit_evict_k, evict_nodes) == 8 && offsetof(fit_evict_k, victims) == 12 &&
+                  offsetof(fit_evict_k, top_prio) == 16 && offsetof(fit_evict_k, members) == 20 &&
+                  offsetof(fit_evict_k, fit) == 24 && offsetof(fit_evict_k, able) == 28 &&
+                  offsetof(fit_evict_k, outranked) == 32 && offsetof(fit_evict_k, reserved) == 36,
+              "fit_evict_k is 40 bytes: code, need, evict_nodes, victims, top_prio, the four counters, reserved");
+
+int preempt_k_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio, int32_t kmax, fit_evict_k* out,
+                   int32_t* out_node, int32_t* out_vic, int32_t* bad) {
+    const int S = preempt_slices(J, c->cls_maxn, c->cus);
+    if (c->pe_part.ensure(preempt_k_partials(J, S, kmax))) return FIT_E_OOM;
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_preempt_k_classify(c->st, c->d_ptab.p, c->np, c->ncomp, d.cpu, d.mem, d.gpu, d.wall, d.part,
+                                             d.nk, kmax, J, out, out_node, out_vic, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_preempt_k(c->st, c->rec.p, c->voff.p, c->vent.p, ec, d.cpu, d.mem, d.gpu, d.wall, d.part,
+                                    prio, kmax, J, c->jcomp.p, jl, live, S, c->pe_part.p, out, out_node, out_vic);
+        });
+}
+
 // fit_load_victims / fit_load_victims_device behind their checks: the row-ordered offsets from the
 // caller's (h_off: host copy, nullptr = every list empty), then the entries from the device CSR.
 // The victims loaded before are replaced from the first write on.
@@ -2457,6 +2489,68 @@ int fit_preempt_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->pe.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_device yet");
     *ms = c->pe.ms;
+    return 0;
+}
+
+// fit_preempt_k / fit_preempt_k_device: fit_preempt's tests, then kmax (nodes_k against kmax is the
+// device's flag word)
+static int check_preempt_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_preempt_k", -1);
+    if (rc) return rc;
+    if (!c->have_vic) return fail(FIT_E_STATE, "fit_load_victims not called");
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+int fit_preempt_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                  const int32_t* wall, const uint16_t* part, const uint16_t* nk, const int32_t* prio, int32_t kmax,
+                  fit_evict_k* out, int32_t* out_node, int32_t* out_victims) {
+    const int rc = check_preempt_k_args(c, j, {cpu, mem, gpu, wall, part, prio, out, out_node, out_victims}, kmax);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the priorities ride beside the packed columns, as fit_preempt's; the picks come back into pinned
+    // memory behind the launches, ahead of query_host's copy of the rows and its synchronisation, and
+    // reach the caller only when the call succeeds
+    const size_t nn = (size_t)j * kmax;
+    if (c->pe_prio.ensure(j) || c->h_pe_prio.ensure(j) || c->pk_node.ensure(nn) || c->pk_vic.ensure(nn) ||
+        c->h_pk_pick.ensure(2 * nn))
+        return FIT_E_OOM;
+    memcpy(c->h_pe_prio.p, prio, sizeof(int32_t) * j);
+    HIP_TRY(hipMemcpyAsync(c->pe_prio.p, c->h_pe_prio.p, sizeof(int32_t) * j, hipMemcpyHostToDevice, c->st));
+    const int r = query_host(
+        c, c->pk, j, cpu, mem, gpu, wall, part, nk, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict_k* rows, int32_t* bad) {
+            const int e = preempt_k_impl(x, n, d, x->pe_prio.p, kmax, rows, x->pk_node.p, x->pk_vic.p, bad);
+            if (e) return e;
+            HIP_TRY(hipMemcpyAsync(x->h_pk_pick.p, x->pk_node.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, x->st));
+            HIP_TRY(hipMemcpyAsync(x->h_pk_pick.p + nn, x->pk_vic.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost,
+                                   x->st));
+            return 0;
+        },
+        bad_when_k_job);
+    if (r) return r;
+    memcpy(out_node, c->h_pk_pick.p, sizeof(int32_t) * nn);
+    memcpy(out_victims, c->h_pk_pick.p + nn, sizeof(int32_t) * nn);
+    return 0;
+}
+
+int fit_preempt_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                         const int32_t* wall, const uint16_t* part, const uint16_t* nk, const int32_t* prio,
+                         int32_t kmax, fit_evict_k* out, int32_t* out_node, int32_t* out_victims) {
+    const int rc = check_preempt_k_args(c, j, {cpu, mem, gpu, wall, part, prio, out, out_node, out_victims}, kmax);
+    if (rc || j == 0) return rc;
+    return query_device(
+        c, c->pk, j, {cpu, mem, gpu, wall, part, nk}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict_k* rows, int32_t* bad) {
+            return preempt_k_impl(x, n, d, prio, kmax, rows, out_node, out_victims, bad);
+        },
+        bad_when_k_job);
+}
+
+int fit_preempt_k_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->pk.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_k_device yet");
+    *ms = c->pk.ms;
     return 0;
 }
 

@@ -376,6 +376,20 @@ hipError_t launch_preempt(hipStream_t st, const NodeRec* rec, const int32_t* vof
                           const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* part,
                           void* out);
 
+// ---- fit_preempt_k (fit_preempt_k.hip) ----------------------------------
+// fit_preempt's codes, victims, slices and chunk; rows of 40 B (fit_evict_k), out_node / out_vic of
+// nj * kmax entries, kmax in [1, FIT_KMAX]; *bad also for a nodes_k above kmax (jk nullptr: all 1)
+hipError_t launch_preempt_k_classify(hipStream_t st, const int32_t* ptab, int32_t np, int ncomp, const int32_t* jcpu,
+                                     const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                     const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t nj, void* out,
+                                     int32_t* out_node, int32_t* out_vic, int8_t* jcomp, int32_t* bad);
+size_t preempt_k_partials(int32_t nj, int slices, int32_t kmax);  // 16-byte words of `part`
+hipError_t launch_preempt_k(hipStream_t st, const NodeRec* rec, const int32_t* voff, const VicEnt* vent,
+                            const ExplainComps& C, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                            const int32_t* jwall, const uint16_t* jpart, const int32_t* jprio, int32_t kmax,
+                            int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
+                            void* part, void* out, int32_t* out_node, int32_t* out_vic);
+
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {
     TRIP_NONE = 0,

@@ -1087,6 +1087,41 @@ int fit_preempt_message(const fit_evict* r, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_evict_k row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
+// with the same numbers and take its sentences.  No device, no context.
+int fit_preempt_k_message(const fit_evict_k* r, char* buf, int32_t buflen) {
+    if (!r || !buf || buflen < 1) return FIT_E_INVAL;
+    std::string s;
+    const auto n = [](int32_t v) { return std::to_string(v); };
+    switch (r->code) {
+        case FIT_PRE_PARTITION:
+        case FIT_PRE_LIMIT_TIME:
+        case FIT_PRE_LIMIT_CPUS:
+        case FIT_PRE_LIMIT_MEM:
+        case FIT_PRE_NO_NODES: {
+            fit_why w;
+            memset(&w, 0, sizeof w);
+            w.code = r->code;
+            return fit_why_message(&w, buf, buflen);
+        }
+        case FIT_PRE_FITS: s = "fits now on " + n(r->need) + " of " + n(r->fit) + "/" + n(r->members) + " nodes"; break;
+        case FIT_PRE_EVICT:
+            s = "fits " + n(r->need) + " nodes after evicting " + n(r->victims) + " lower-priority jobs on " +
+                n(r->evict_nodes) + " of them (highest priority " + n(r->top_prio) + "): " + n(r->fit) + " fit now, " +
+                n(r->able) + " can be freed, of " + n(r->members) + " nodes";
+            break;
+        case FIT_PRE_NONE:
+            s = "needs " + n(r->need) + " nodes: " + n(r->fit) + " fit now, " + n(r->able) + " can be freed, of " +
+                n(r->members) + " nodes";
+            if (r->outranked != 0) s += ": " + n(r->outranked) + " held by jobs of equal or higher priority";
+            break;
+        default: return FIT_E_INVAL;
+    }
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 // A fit_free row as one line; the texts are fixed in include/fitgpu.h.  No device, no context.
 int fit_free_message(const fit_free* r, char* buf, int32_t buflen) {
     if (!r || !buf || buflen < 1) return FIT_E_INVAL;

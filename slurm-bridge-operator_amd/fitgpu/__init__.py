@@ -39,7 +39,7 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom,
                    FIT_HOLD_HELD, FIT_HOLD_REFUSED, FIT_HOLD_SKIPPED, FitFree,
                    FIT_PRE_EVICT, FIT_PRE_FITS, FIT_PRE_LIMIT_CPUS, FIT_PRE_LIMIT_MEM, FIT_PRE_LIMIT_TIME,
-                   FIT_PRE_NO_NODES, FIT_PRE_NONE, FIT_PRE_PARTITION, FitEvict)
+                   FIT_PRE_NO_NODES, FIT_PRE_NONE, FIT_PRE_PARTITION, FitEvict, FitEvictK)
 
 __all__ = [
     "Engine", "FitError", "ErrDurationIsUnlimited", "ParseDuration", "parse_resources", "parse_nodes",
@@ -58,7 +58,7 @@ __all__ = [
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
     "FIT_HOLD_HELD", "FIT_HOLD_REFUSED", "FIT_HOLD_SKIPPED",
     "free_message", "FREE_DTYPE", "FitFree",
-    "preempt_message", "EVICT_DTYPE", "FitEvict", "FIT_PRE_FITS", "FIT_PRE_PARTITION", "FIT_PRE_LIMIT_TIME",
+    "preempt_message", "EVICT_DTYPE", "FitEvict", "preempt_k_message", "EVICT_K_DTYPE", "FitEvictK", "FIT_PRE_FITS", "FIT_PRE_PARTITION", "FIT_PRE_LIMIT_TIME",
     "FIT_PRE_LIMIT_CPUS", "FIT_PRE_LIMIT_MEM", "FIT_PRE_NO_NODES", "FIT_PRE_EVICT", "FIT_PRE_NONE",
 ]
 
@@ -436,6 +436,21 @@ def preempt_message(row) -> str:
     r = FitEvict(*(int(get(n)) for n, _ in FitEvict._fields_))
     buf = C.create_string_buffer(256)
     n = check(lib().fit_preempt_message(C.byref(r), buf, len(buf)), "fit_preempt_message")
+    return buf.raw[:n].decode()
+
+
+# -------------------------------------------------------------------------------- preempt_k
+# one fit_evict_k row (include/fitgpu.h), 40 bytes of int32: what Engine.preempt_k returns
+EVICT_K_DTYPE = np.dtype([(n, np.int32) for n, _ in FitEvictK._fields_])
+
+
+def preempt_k_message(row) -> str:
+    """A fit_evict_k row (an element of a preempt_k() result, or any mapping / object with its
+    fields) as one line of text (fit_preempt_k_message); needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    r = FitEvictK(*(int(get(n)) for n, _ in FitEvictK._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_preempt_k_message(C.byref(r), buf, len(buf)), "fit_preempt_k_message")
     return buf.raw[:n].decode()
 
 
@@ -908,6 +923,48 @@ class Engine:
         """Device time in ms of the last successful preempt_device (fit_preempt_ms)."""
         ms = C.c_double()
         check(lib().fit_preempt_ms(self._h, C.byref(ms)), "fit_preempt_ms")
+        return ms.value
+
+    # ---- which victims to evict so that a multi-node job fits (DESIGN.md §2m) -----------------
+    def preempt_k(self, jobs, prio, kmax: int | None = None):
+        """Every job judged alone against the current node table and the loaded victims, on
+        max(jobs.nodes_k, 1) distinct nodes at once (fit_preempt_k): (rows[J] of EVICT_K_DTYPE,
+        nodes[J, kmax], victims[J, kmax]).  A FITS or EVICT row's picks in key order with the entries
+        of each node's list to evict (0: it fits now); -1 and 0 elsewhere.  Changes nothing.  kmax
+        None: the largest nodes_k of the batch (at least 1)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = None if jobs.nodes_k is None else np.ascontiguousarray(jobs.nodes_k, np.uint16)  # None: all 1
+        prio = np.ascontiguousarray(prio, np.int32)
+        j = len(part)
+        if len(prio) != j or (k is not None and len(k) != j):
+            raise ValueError("prio and nodes_k must have one entry per job")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j and k is not None else 1
+        out = np.zeros(j, EVICT_K_DTYPE)
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        victims = np.zeros((j, max(int(kmax), 0)), np.int32)
+        check(lib().fit_preempt_k(self._h, j, *[_ptr(c) for c in cols], _ptr(part), _ptr(k) if k is not None else None,
+                                  _ptr(prio), int(kmax), _ptr(out), _ptr(nodes), _ptr(victims)), "fit_preempt_k")
+        return out, nodes, victims
+
+    def preempt_k_device(self, cpu, mem, gpu, wall, part, nodes_k, prio, out, out_node, out_victims, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1); writes out
+        (J rows of 10 int32, the fields of EVICT_K_DTYPE in order), out_node and out_victims (J * kmax
+        int32 each).  Returns the device time of its launches in ms (HIP events on the context's
+        stream, fit_preempt_k_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_preempt_k_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                         _ptr(nodes_k) if nodes_k is not None else None, _ptr(prio), int(kmax),
+                                         _ptr(out), _ptr(out_node), _ptr(out_victims)), "fit_preempt_k_device")
+        if j == 0:
+            return 0.0
+        return self.preempt_k_ms()
+
+    def preempt_k_ms(self):
+        """Device time in ms of the last successful preempt_k_device (fit_preempt_k_ms)."""
+        ms = C.c_double()
+        check(lib().fit_preempt_k_ms(self._h, C.byref(ms)), "fit_preempt_k_ms")
         return ms.value
 
     # ---- free capacity per partition and slot (DESIGN.md §2k) --------------------------------

@@ -51,6 +51,7 @@ EXPORTS = [
     "fit_free_tl", "fit_free_tl_device", "fit_free_tl_ms", "fit_free_message",
     "fit_load_victims", "fit_load_victims_device", "fit_preempt", "fit_preempt_device", "fit_preempt_ms",
     "fit_preempt_message",
+    "fit_preempt_k", "fit_preempt_k_device", "fit_preempt_k_ms", "fit_preempt_k_message",
 ]
 
 
@@ -144,6 +145,11 @@ class FitEvict(C.Structure):  # fit_evict: one row of fit_preempt, 32 bytes
     _fields_ = [(n, C.c_int32) for n in ("code", "node", "victims", "top_prio", "members", "fit", "able", "outranked")]
 
 
+class FitEvictK(C.Structure):  # fit_evict_k: one row of fit_preempt_k, 40 bytes; the codes are FIT_PRE_*
+    _fields_ = [(n, C.c_int32) for n in ("code", "need", "evict_nodes", "victims", "top_prio", "members", "fit", "able",
+                                         "outranked", "reserved")]
+
+
 class FitFree(C.Structure):  # fit_free: one (partition, slot) row of fit_free_tl, 40 bytes
     _fields_ = [("cpu", C.c_int64), ("mem", C.c_int64), ("gpu", C.c_int64), ("nodes", C.c_int32),
                 ("max_cpu", C.c_int32), ("max_mem", C.c_int32), ("max_gpu", C.c_int32)]
@@ -232,6 +238,10 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P]
         L.fit_preempt_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_preempt_message.argtypes = [C.POINTER(FitEvict), C.c_char_p, i32]
+        for name in ("fit_preempt_k", "fit_preempt_k_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P, i32, P, P, P]
+        L.fit_preempt_k_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_preempt_k_message.argtypes = [C.POINTER(FitEvictK), C.c_char_p, i32]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

@@ -728,6 +728,83 @@ func PreemptMessage(r Evict) string {
 	return string(buf[:int(n)])
 }
 
+// EvictK is one fit_evict_k row: the job judged alone on max(NodesK, 1) distinct nodes at once
+// against the current node table and the loaded victims (DESIGN.md §2m).  Code is one of Pre*.
+type EvictK struct {
+	Code       int32 // Pre*: PreFits with Fit >= Need, PreEvict with Fit < Need <= Fit + Able, else PreNone
+	Need       int32 // max(NodesK, 1)
+	EvictNodes int32 // picks that need an eviction
+	Victims    int32 // entries to evict, summed over the picks
+	TopPrio    int32 // the highest priority evicted; 0 when EvictNodes == 0
+	Members    int32 // as Evict
+	Fit        int32
+	Able       int32
+	Outranked  int32
+	Reserved   int32 // 0
+}
+
+func goEvictK(r *C.fit_evict_k) EvictK {
+	return EvictK{Code: int32(r.code), Need: int32(r.need), EvictNodes: int32(r.evict_nodes), Victims: int32(r.victims),
+		TopPrio: int32(r.top_prio), Members: int32(r.members), Fit: int32(r.fit), Able: int32(r.able),
+		Outranked: int32(r.outranked), Reserved: int32(r.reserved)}
+}
+
+// PreemptK is Preempt for jobs of NodesK nodes (fit_preempt_k): for every job, judged alone, the Need
+// nodes with the smallest keys — every node that fits now first, then the nodes whose eviction costs
+// least.  nodes and victims have kmax entries per job: a PreFits or PreEvict row's picks in key order
+// and the entries of each pick's list to evict, [Off[node], Off[node]+victims), 0 for a node that
+// fits now; -1 and 0 elsewhere.  It changes nothing and evicts nothing.  prio has one entry per job;
+// NodesK may be empty (every job takes one node).
+func (e *Engine) PreemptK(j Jobs, prio []int32, kmax int) ([]EvictK, []int32, []int32, error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return nil, nil, nil, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part), len(prio)) ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, nil, nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil, nil, nil
+	}
+	var nk *C.uint16_t // NULL: every job takes one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	rows := make([]C.fit_evict_k, cnt)
+	nodes, victims := make([]int32, cnt*kmax), make([]int32, cnt*kmax)
+	rc := C.fit_preempt_k(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])), nk,
+		(*C.int32_t)(unsafe.Pointer(&prio[0])), C.int32_t(kmax), &rows[0],
+		(*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&victims[0])))
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	out := make([]EvictK, cnt)
+	for i := range rows {
+		out[i] = goEvictK(&rows[i])
+	}
+	return out, nodes, victims, nil
+}
+
+// PreemptKMessage is the row as one line (fit_preempt_k_message: "fits 4 nodes after evicting 5
+// lower-priority jobs on 3 of them (highest priority 10): 1 fit now, 37 can be freed, of 512 nodes");
+// "" for a row with an unknown code.
+func PreemptKMessage(r EvictK) string {
+	c := C.fit_evict_k{code: C.int32_t(r.Code), need: C.int32_t(r.Need), evict_nodes: C.int32_t(r.EvictNodes),
+		victims: C.int32_t(r.Victims), top_prio: C.int32_t(r.TopPrio), members: C.int32_t(r.Members),
+		fit: C.int32_t(r.Fit), able: C.int32_t(r.Able), outranked: C.int32_t(r.Outranked),
+		reserved: C.int32_t(r.Reserved)}
+	buf := make([]byte, 256)
+	n := C.fit_preempt_k_message(&c, (*C.char)(unsafe.Pointer(&buf[0])), C.int32_t(len(buf)))
+	if n < 0 {
+		return ""
+	}
+	return string(buf[:int(n)])
+}
+
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
 // nodes that are open there (DESIGN.md §2k).
 type Free struct {
