@@ -10,15 +10,16 @@
 //   launch_joblists : the jobs of each component, in index order inside a component
 //   k_ptlk_commit   : ONE workgroup per partition component, looping over its component's jobs of
 //                     the chunk in order.  Per job: (count) threads stride over the component's
-//                     nodes, walk each whole run list and add +1 / -1 at the ends of every stretch
-//                     of feasible starts to a difference array in LDS; (pick) one wave takes the
-//                     prefix sum, 64 slots per step, and leaves at the first s with cnt >= need;
-//                     (nodes) the count walk also scores each node's FIRST window, and a thread
-//                     keeps its 8 smallest keys sorted in registers: when no node is free before
-//                     the start these are the answer; otherwise threads evaluate the one window
-//                     [start, start + d) on their nodes again.  `need` rounds of an LDS 64-bit
-//                     minimum take the workgroup's smallest; (reserve) one wave per pick reserves
-//                     with tl_reserve_any and refreshes the node's header (tl_refresh_head).
+//                     nodes, visit each whole run list (tl_each_run) and add +1 / -1 at the ends
+//                     of every stretch of feasible starts to a difference array in LDS; (pick) one
+//                     wave finds the first s with cnt >= need (tl_first_start); (nodes) the count
+//                     walk also scores each node's FIRST window, and a thread keeps its 8 smallest
+//                     keys (tl_keep): when no node is free before the start these are the answer;
+//                     otherwise threads evaluate the one window [start, start + d) on their nodes
+//                     again (tl_window).  `need` rounds of an LDS 64-bit minimum take the
+//                     workgroup's smallest; (reserve) one wave per pick reserves with tl_reserve_any and refreshes the
+//                     node's header (tl_refresh_head).
+// The run-list pieces named in brackets are fit_tl_walk.h's, shared with fit_when_k.hip.
 // A component's rows are read and written by its workgroup alone, so nothing here waits for another
 // workgroup: no persistent grid, no launch lock, no watchdog.  Between jobs the waves of the
 // workgroup hand the run lists on through __syncthreads(), i.e. a workgroup-scope release before and
@@ -35,7 +36,6 @@
 namespace fitgpu {
 
 constexpr int PTLK_RWAVES = FIT_KMAX;  // waves that reserve side by side, one pick each
-static_assert(TL_HEAD % 4 == 0 && TL_MAX_SLOTS % 4 == 0, "the walks load four Seg at a time inside a slab row");
 static_assert(PTLK_THREADS % 64 == 0 && PTLK_THREADS <= 1024, "whole waves, one workgroup");
 
 __global__ __launch_bounds__(256) void k_ptlk_classify(
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
         const int q = jl[t];
         const int32_t cpu = jcpu[q], mem = jmem[q], gpu = jgpu[q];
         const int32_t need = tl_need(jk, q, kmax);
-        const int32_t d = tl_dur(jwall[q], slot_min);  // k_whenk_classify's `dur`
+        const int32_t d = tl_dur(jwall[q], slot_min);  // fit_when_k's `dur`
         const uint32_t pbit = 1u << (jpart[q] & 31);
         if (d > H) continue;  // no window inside the horizon: unplaced, nothing touched
         // the last job's readers of pick[] are behind its closing barrier; two barriers lie between
@@ -108,15 +108,15 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
         for (int i = 0; i < FIT_KMAX; ++i) key[i] = KEY_INF;
         for (int x = nb + tid; x < ne; x += nt) {
             const TlHdr h = hdr[x];
-            // the header's column ceilings reject a node without a walk (when_node's rule)
+            // the header's column ceilings reject a node without a walk
             if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
             const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
             const int cn = min(h.cnt, TL_MAX_SLOTS);
             int32_t s0 = 0, ra = -1;  // start of the current run, of the current feasible stretch (-1: none)
             int32_t mc = 0, mm = 0, mg = 0;         // minima of the current stretch's runs so far
             int32_t ks = -1, kc = 0, km = 0, kg = 0;  // the first window: its start and minima, frozen
-            auto step = [&](bool vr, int32_t rc, int32_t rm, int32_t rg, int32_t e) {
-                const bool f = vr & (rc >= cpu) & (rm >= mem) & (rg >= gpu);
+            auto step = [&](const Seg& r, bool vr = true) {  // vr false: behind the last run
+                const bool f = vr & (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
                 if (!f && ra >= 0) {
                     if (s0 - ra >= d) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
                         atomicAdd(&diff[ra], 1);
@@ -124,13 +124,13 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
                     }
                     ra = -1;
                 }
-                const int32_t e1 = min(max(e, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
+                const int32_t e1 = min(max(r.end, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
                 if (f && s0 < H) {
                     const bool nw = ra < 0;
                     ra = nw ? s0 : ra;
-                    mc = nw ? rc : min(mc, rc);
-                    mm = nw ? rm : min(mm, rm);
-                    mg = nw ? rg : min(mg, rg);
+                    mc = nw ? r.cpu : min(mc, r.cpu);
+                    mm = nw ? r.mem : min(mm, r.mem);
+                    mg = nw ? r.gpu : min(mg, r.gpu);
                     if (ks < 0 && e1 - ra >= d) {  // the run that holds slot ra + d - 1 closes the first window
                         ks = ra;
                         kc = mc;
@@ -140,54 +140,19 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
                 }
                 s0 = e1;
             };
-#pragma unroll
-            for (int i = 0; i < TL_HEAD; ++i)
-                if (i < cn) step(true, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, h.head[i].end);
-            for (int i = TL_HEAD; i < cn; i += 4) {  // four Seg per wait, as when_node
-                Seg r4[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (i + k < cn) step(true, r4[k].cpu, r4[k].mem, r4[k].gpu, r4[k].end);
-            }
-            step(false, 0, 0, 0, H);
+            tl_each_run(h, sg, cn, step);
+            step(Seg{H, 0, 0, 0}, false);
             if (ks < 0) continue;
-            uint64_t k = tl_key(ks, kc, km, kg, cpu, mem, gpu, (uint32_t)x);
-#pragma unroll
-            for (int i = 0; i < FIT_KMAX; ++i) {  // sorted insert: k carries the larger one on
-                const uint64_t lo2 = min(k, key[i]);
-                k = max(k, key[i]);
-                key[i] = lo2;
-            }
+            tl_keep(key, tl_key(ks, kc, km, kg, cpu, mem, gpu, (uint32_t)x));
         }
         __syncthreads();
 
-        // ---- pick: cnt(s) is the prefix sum of the differences; starts lie in [0, H - d]
+        // ---- pick: the first start with `need` nodes free together
         if (wave == 0) {
-            int32_t carry = 0, first = -1, early = 0;
-            for (int base = 0; base < H; base += 64) {
-                const int s = base + lane;
-                int32_t v = s < H ? diff[s] : 0;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int32_t u = __shfl_up(v, off);
-                    if (lane >= off) v += u;
-                }
-                v += carry;  // cnt(s)
-                const uint64_t hit = __ballot(s < H && v >= need);
-                const uint64_t some = __ballot(s < H && v > 0);
-                if (hit) {
-                    first = base + __builtin_ctzll(hit);
-                    early |= (some & ((1ull << __builtin_ctzll(hit)) - 1ull)) != 0;
-                    break;
-                }
-                early |= some != 0;
-                carry = __shfl(v, 63);
-            }
+            const TlStart f = tl_first_start(diff, H, need, lane);
             if (lane == 0) {
-                sh[0] = first;
-                sh[1] = early;  // some node is free before the start: its first window is not the job's
+                sh[0] = f.start;
+                sh[1] = f.early;  // some node is free before the start: its first window is not the job's
             }
         }
         __syncthreads();
@@ -202,7 +167,7 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
         // ---- nodes: when no node is free before the start, the members free from it are exactly those
         // whose earliest start it is, and their windows are the ones the count walk scored: the keys are
         // there, in (score, position) order behind the common start.  Otherwise the one window
-        // [start, start + d) gives feasibility and the minima (k_whenk_nodes).
+        // [start, start + d) gives feasibility and the minima.
         const int32_t stop = start + d;  // <= H: the differences only mark starts s with s + d <= H
         if (sh[1]) {
 #pragma unroll
@@ -212,37 +177,9 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
                 if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
                 const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
                 const int cn = min(h.cnt, TL_MAX_SLOTS);
-                int32_t mc = 0x7fffffff, mm = 0x7fffffff, mg = 0x7fffffff;
-                bool ok = true, closed = false;  // closed: the runs seen cover the window
-                // runs end in increasing order and the walk stops at the first that reaches `stop`, so a run
-                // meets the window exactly when it ends behind `start`
-                auto run = [&](const Seg& r) {
-                    if (r.end <= start) return;
-                    ok = (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
-                    mc = min(mc, r.cpu);
-                    mm = min(mm, r.mem);
-                    mg = min(mg, r.gpu);
-                    closed = r.end >= stop;
-                };
-#pragma unroll
-                for (int i = 0; i < TL_HEAD; ++i)
-                    if (i < cn && ok && !closed) run(h.head[i]);
-                for (int i = TL_HEAD; i < cn && ok && !closed; i += 4) {
-                    Seg r4[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (i + k < cn && ok && !closed) run(r4[k]);
-                }
-                if (!ok || !closed) continue;
-                uint64_t k = tl_key(start, mc, mm, mg, cpu, mem, gpu, (uint32_t)x);
-#pragma unroll
-                for (int i = 0; i < FIT_KMAX; ++i) {  // sorted insert: k carries the larger one on
-                    const uint64_t lo2 = min(k, key[i]);
-                    k = max(k, key[i]);
-                    key[i] = lo2;
-                }
+                int32_t mc, mm, mg;
+                if (!tl_window(h, sg, cn, start, stop, cpu, mem, gpu, mc, mm, mg)) continue;
+                tl_keep(key, tl_key(start, mc, mm, mg, cpu, mem, gpu, (uint32_t)x));
             }
         }
         // either way a key that counts carries `start` in its top bits; a later first window does not

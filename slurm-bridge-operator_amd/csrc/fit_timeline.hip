@@ -54,7 +54,7 @@ __device__ __forceinline__ uint64_t tl_eval(const Seg* sg, int cnt, bool live, i
         if (!__ballot(w.live && i < cnt)) break;
         if (w.live && i < cnt) {
             const Seg g = sg[i];
-            tl_step(w, g.end, g.cpu, g.mem, g.gpu, jc, jm, jg, d, H, lim, pos);
+            tl_step(w, g.end, g.cpu, g.mem, g.gpu, jc, jm, jg, d, H, lim);
         }
     }
     return tl_walk_key(w, jc, jm, jg, pos);
@@ -74,7 +74,7 @@ __device__ __forceinline__ uint64_t tl_eval4(const Seg* sg, int cnt, int cap, bo
         for (int u = 0; u < 4; ++u) g[u] = sg[min(i + u, cap - 1)];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            tl_step_v(w, i + u < cnt, g[u].end, g[u].cpu, g[u].mem, g[u].gpu, jc, jm, jg, d, H, lim, pos);
+            tl_step_v(w, i + u < cnt, g[u].end, g[u].cpu, g[u].mem, g[u].gpu, jc, jm, jg, d, H, lim);
     }
     return tl_walk_key(w, jc, jm, jg, pos);
 }
@@ -168,7 +168,7 @@ __device__ __forceinline__ void tl_scan_node(const TlHdr& h, int x, const JobRec
     for (int i = 0; i < TL_HEAD; ++i)
         if (i < cn)
             tl_step(w, h.head[i].end, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, J.cpu, J.mem,
-                    J.gpu, J.wall, H, lim, (uint32_t)x);
+                    J.gpu, J.wall, H, lim);
     if (cn > TL_HEAD) {
         const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
         for (int b = TL_HEAD; b < cn; b += TL_HEAD) {
@@ -186,7 +186,7 @@ __device__ __forceinline__ void tl_scan_node(const TlHdr& h, int x, const JobRec
             for (int i = 0; i < TL_HEAD; ++i)
                 if (b + i < cn)
                     tl_step(w, r4[i].end, r4[i].cpu, r4[i].mem, r4[i].gpu, J.cpu, J.mem, J.gpu,
-                            J.wall, H, lim, (uint32_t)x);
+                            J.wall, H, lim);
         }
     }
     const uint64_t wk = tl_walk_key(w, J.cpu, J.mem, J.gpu, (uint32_t)x);

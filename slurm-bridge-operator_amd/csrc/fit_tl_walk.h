@@ -1,7 +1,11 @@
-// fit_tl_walk.h — the exact earliest-start walk over one node's run list (SPEC §2b; DESIGN.md
-// §3.8) and its key, shared by the backfill engines (fit_timeline.hip), the multi-node backfill
-// (fit_place_tl_k.hip) and the read-only queries (fit_when.hip, fit_when_k.hip).  Every function is
+// fit_tl_walk.h — reading one node's run list (SPEC §2b).  Every function is
 // __forceinline__.
+//   tl_key, TlWalk, tl_step(_v), tl_walk_key : the exact earliest-start walk and its key, for the
+//       backfill engines (fit_timeline.hip) and fit_when.hip; the key also for the two below
+//   tl_each_run, TL_WINDOW / tl_window, tl_keep, tl_first_start : what the multi-node kernels
+//       (fit_when_k.hip, fit_place_tl_k.hip) share: the visit of every run, header then slab; the
+//       one window [start, stop); a lane's sorted key list; the first common start from a
+//       difference array
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +42,7 @@ __device__ __forceinline__ TlWalk tl_walk0(bool live) {
 // rest of the walk, so only the key and liveness need the gate).
 __device__ __forceinline__ void tl_step_v(TlWalk& w, bool vld, int32_t end, int32_t c, int32_t m,
                                           int32_t g, int32_t jc, int32_t jm, int32_t jg, int32_t d,
-                                          int32_t H, int32_t lim, uint32_t pos) {
+                                          int32_t H, int32_t lim) {
     const bool f = (c >= jc) & (m >= jm) & (g >= jg);
     const bool nw = w.ra < 0;
     const int32_t ra = f ? (nw ? w.a : w.ra) : -1;
@@ -61,14 +65,125 @@ __device__ __forceinline__ void tl_step_v(TlWalk& w, bool vld, int32_t end, int3
 
 __device__ __forceinline__ void tl_step(TlWalk& w, int32_t end, int32_t c, int32_t m, int32_t g,
                                         int32_t jc, int32_t jm, int32_t jg, int32_t d, int32_t H,
-                                        int32_t lim, uint32_t pos) {
-    tl_step_v(w, true, end, c, m, g, jc, jm, jg, d, H, lim, pos);
+                                        int32_t lim) {
+    tl_step_v(w, true, end, c, m, g, jc, jm, jg, d, H, lim);
 }
 
 // the walk's key (KEY_INF: no window found)
 __device__ __forceinline__ uint64_t tl_walk_key(const TlWalk& w, int32_t jc, int32_t jm,
                                                 int32_t jg, uint32_t pos) {
     return w.got ? tl_key(w.kra, w.kmc, w.kmm, w.kmg, jc, jm, jg, pos) : KEY_INF;
+}
+
+// ---- the multi-node kernels' pieces (fit_when_k.hip, fit_place_tl_k.hip) ----------------------
+
+// Every run of one node, in order: the TL_HEAD runs of the header copy h, then the slab row sg four
+// Seg per wait; cn = min(h.cnt, TL_MAX_SLOTS).  f(const Seg&) is called per run.  A batch is loaded
+// whole, runs behind the list's end included (f never sees them): it stays inside the slab row
+// because 4 divides TL_HEAD and TL_MAX_SLOTS, whatever cn is.  TL_WINDOW's loops rest on the same.
+static_assert(TL_HEAD % 4 == 0 && TL_MAX_SLOTS % 4 == 0, "the visits load four Seg at a time inside a slab row");
+template <class F>
+__device__ __forceinline__ void tl_each_run(const TlHdr& h, const Seg* sg, int cn, F f) {
+#pragma unroll
+    for (int i = 0; i < TL_HEAD; ++i)
+        if (i < cn) f(h.head[i]);
+    for (int i = TL_HEAD; i < cn; i += 4) {
+        Seg r4[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k < cn) f(r4[k]);
+    }
+}
+
+// The one window [start, stop) of a node: declares mc, mm, mg, the minima of the runs that meet the
+// window, and fits: every one of them holds (cpu, mem, gpu) and the list reaches `stop`.  The visit
+// is tl_each_run's, left at the first run that fails or closes the window.  A macro because
+// k_whenk_nodes is 8 % slower through the function below and 24 % slower with the visit as a gated
+// tl_each_run, the same loops scheduled differently (profiles/tl_runs_ab.txt); k_ptlk_commit, which
+// is bound by its SGPRs, is the faster one through the function.
+#define TL_WINDOW(h, sg, cn, start, stop, cpu, mem, gpu, mc, mm, mg, fits)                               \
+    int32_t mc = 0x7fffffff, mm = 0x7fffffff, mg = 0x7fffffff;                                           \
+    bool fits;                                                                                           \
+    {                                                                                                    \
+        bool ok = true, closed = false; /* closed: the runs seen cover the window */                     \
+        /* runs end in increasing order and the walk stops at the first that reaches `stop`, so a run */ \
+        /* meets the window exactly when it ends behind `start` */                                       \
+        auto run = [&](const Seg& r) {                                                                   \
+            if (r.end <= start) return;                                                                  \
+            ok = (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);                                       \
+            mc = min(mc, r.cpu);                                                                         \
+            mm = min(mm, r.mem);                                                                         \
+            mg = min(mg, r.gpu);                                                                         \
+            closed = r.end >= stop;                                                                      \
+        };                                                                                               \
+        _Pragma("unroll") for (int i = 0; i < TL_HEAD; ++i)                                              \
+            if (i < cn && ok && !closed) run(h.head[i]);                                                 \
+        for (int i = TL_HEAD; i < cn && ok && !closed; i += 4) {                                         \
+            Seg r4[4];                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];                             \
+            _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                \
+                if (i + k < cn && ok && !closed) run(r4[k]);                                             \
+        }                                                                                                \
+        fits = ok && closed;                                                                             \
+    }
+__device__ __forceinline__ bool tl_window(const TlHdr& h, const Seg* sg, int cn, int32_t start, int32_t stop,
+                                          int32_t cpu, int32_t mem, int32_t gpu, int32_t& mc, int32_t& mm,
+                                          int32_t& mg) {
+    TL_WINDOW(h, sg, cn, start, stop, cpu, mem, gpu, c, m, g, fits)
+    mc = c;
+    mm = m;
+    mg = g;
+    return fits;
+}
+
+// Keep k if it is among the K smallest keys seen: key[] is a lane's sorted register list, k carries
+// the larger one on.  Beside topk_insert (fit_common.h: compares first, then a clamp per entry, tuned
+// for the scan) and PreTop (fit_preempt_k.hip: 128-bit keys), which stay as they are.
+template <int K>
+__device__ __forceinline__ void tl_keep(uint64_t (&key)[K], uint64_t k) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const uint64_t lo = min(k, key[i]);
+        k = max(k, key[i]);
+        key[i] = lo;
+    }
+}
+
+// One wave over a difference array of H + 1 words (HBM or LDS): cnt(s), the number of nodes free for
+// a start at s, is the prefix sum, taken 64 slots per step.  Starts lie in [0, H - d]; word H only
+// takes -1s.  start: the first s with cnt(s) >= need (-1: none), ready: cnt(start), now: cnt(0),
+// early: some s < start has cnt(s) > 0.  A caller pays for the results it reads only.
+struct TlStart {
+    int32_t start, ready, now;
+    bool early;
+};
+__device__ __forceinline__ TlStart tl_first_start(const int32_t* diff, int32_t H, int32_t need, int lane) {
+    TlStart r{-1, 0, diff[0], false};  // cnt(0) is the first word itself (H >= 1)
+    int32_t carry = 0;
+    for (int base = 0; base < H; base += 64) {
+        const int s = base + lane;
+        int32_t v = s < H ? diff[s] : 0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t u = __shfl_up(v, off);
+            if (lane >= off) v += u;
+        }
+        v += carry;  // cnt(s)
+        const uint64_t hit = __ballot(s < H && v >= need);
+        const uint64_t some = __ballot(s < H && v > 0);
+        if (hit) {
+            const int first = __builtin_ctzll(hit);
+            r.start = base + first;
+            r.ready = __shfl(v, first);
+            r.early |= (some & ((1ull << first) - 1ull)) != 0;
+            break;
+        }
+        r.early |= some != 0;
+        carry = __shfl(v, 63);
+    }
+    return r;
 }
 
 }  // namespace fitgpu

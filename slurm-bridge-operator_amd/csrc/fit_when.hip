@@ -85,8 +85,7 @@ __device__ __forceinline__ void when_node(const TlHdr& h, int x, const Seg* __re
     // header's scalar loads, so they go out together
 #pragma unroll
     for (int i = 0; i < TL_HEAD; ++i)
-        tl_step_v(w, i < cn, h.head[i].end, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, cpu, mem, gpu, d, H, H,
-                  (uint32_t)x);
+        tl_step_v(w, i < cn, h.head[i].end, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, cpu, mem, gpu, d, H, H);
     if (cn > TL_HEAD) {
         const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
         for (int b = TL_HEAD; b < cn; b += 4) {
@@ -96,8 +95,7 @@ __device__ __forceinline__ void when_node(const TlHdr& h, int x, const Seg* __re
             for (int i = 0; i < 4; ++i) r4[i] = sg[b + i];  // inside the slab row (4 | TL_MAX_SLOTS)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (b + i < cn) tl_step(w, r4[i].end, r4[i].cpu, r4[i].mem, r4[i].gpu, cpu, mem, gpu, d, H, H,
-                                        (uint32_t)x);
+                if (b + i < cn) tl_step(w, r4[i].end, r4[i].cpu, r4[i].mem, r4[i].gpu, cpu, mem, gpu, d, H, H);
         }
     }
     best = min(best, tl_walk_key(w, cpu, mem, gpu, (uint32_t)x));

@@ -8,23 +8,24 @@
 //   k_whenk_classify : per job, the partition-limit code (job_limit), `dur`, `need`, the row's
 //                      counters zeroed and the job's component
 //   k_whenk_count    : one workgroup per (group of 8 jobs, node slice), threads = nodes.  A thread
-//                      loads its node's WHOLE run list once and steps the group's jobs over it:
-//                      for every maximal feasible stretch [a, b) of at least d slots of a job, +1
-//                      at a and -1 at b - d + 1 of that job's difference array in LDS (H + 1
-//                      words each, 32.8 KB for the group).  The workgroup flushes the non-zero
-//                      words to the jobs' arrays in HBM with returnless integer atomics,
+//                      visits its node's WHOLE run list once (tl_each_run) and steps the group's
+//                      jobs over it: for every maximal feasible stretch [a, b) of at least d slots
+//                      of a job, +1 at a and -1 at b - d + 1 of that job's difference array in LDS
+//                      (H + 1 words each, 32.8 KB for the group).  The workgroup flushes the
+//                      non-zero words to the jobs' arrays in HBM with returnless integer atomics,
 //                      lane-contiguous, and adds `members` / `hosts`.  Above 8 jobs on several
 //                      components the jobs come in component order (launch_joblists), so that a
 //                      group shares its nodes.
-//   k_whenk_pick     : one wave per job: the prefix sum of the differences, 64 slots per step, is
-//                      cnt(s); the first s with cnt >= need is the start.  Stores start, ready, now.
+//   k_whenk_pick     : one wave per job: tl_first_start over the job's differences.  Stores
+//                      start, ready, now.
 //   k_whenk_nodes    : one workgroup per (job with a start, node slice), threads = nodes: the one
-//                      window [start, start + d) on the run list gives feasibility and the minima,
-//                      hence score << TL_POS_BITS | pos.  A thread keeps its 8 smallest keys sorted
-//                      in registers; the workgroup extracts its `need` smallest through an LDS
+//                      window [start, start + d) (TL_WINDOW) gives feasibility and the minima,
+//                      hence score << TL_POS_BITS | pos.  A thread keeps its 8 smallest keys
+//                      (tl_keep); the workgroup extracts its `need` smallest through an LDS
 //                      64-bit min per round and stores them per (job, slice).
 //   k_whenk_final    : one wave per job: the `need` smallest of the slices' keys -> out_node
 //                      (TlHdr::orig, key order), wait_min and the code.
+// The run-list pieces named in brackets are fit_tl_walk.h's, shared with fit_place_tl_k.hip.
 // Cross-workgroup traffic is integer atomicAdd (commutative) or disjoint stores, so rows are exact
 // and reproducible.  No cross-workgroup wait of any kind: no watchdog, no persistent-launch lock.
 #include <hip/hip_runtime.h>
@@ -47,7 +48,6 @@ struct EtaKRow {
 static_assert(sizeof(EtaKRow) == 40 && offsetof(EtaKRow, members) == 20, "fit_eta_k is 40 bytes");
 static_assert(WHENK_KEYS == FIT_KMAX, "a slice keeps one key per node of the widest job");
 static_assert(WHENK_MAX_SLICES * WHENK_KEYS <= 128, "k_whenk_final holds two keys per lane");
-static_assert(TL_HEAD % 4 == 0 && TL_MAX_SLOTS % 4 == 0, "the walks load four Seg at a time inside a slab row");
 
 __global__ __launch_bounds__(256) void k_whenk_classify(
     const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
         if (!query_slice(C, c, a, b)) continue;
         for (int x = a + threadIdx.x; x < b; x += WK_THREADS) {
             const TlHdr h = hdr[x];
-            // members; the header's column ceilings and d <= H reject a node without a walk (when_node's rule)
+            // members; the header's column ceilings and d <= H reject a node without a walk
             uint32_t lv = 0;
 #pragma unroll
             for (int g = 0; g < WK_GROUP; ++g) {
@@ -147,12 +147,12 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
 #pragma unroll
             for (int g = 0; g < WK_GROUP; ++g) ra[g] = -1;
             uint32_t any = 0;
-            // one run [s0, e) with (rc, rm, rg) free, vr false behind the last run: per job, the run holds
-            // the demand or the job's stretch ends at s0
-            auto step = [&](bool vr, int32_t rc, int32_t rm, int32_t rg, int32_t e) {
+            // one run [s0, r.end) with r's columns free, vr false behind the last run: per job, the run
+            // holds the demand or the job's stretch ends at s0
+            auto step = [&](const Seg& r, bool vr = true) {
 #pragma unroll
                 for (int g = 0; g < WK_GROUP; ++g) {
-                    const bool f = vr & (bool)((lv >> g) & 1u) & (rc >= cpu[g]) & (rm >= mem[g]) & (rg >= gpu[g]);
+                    const bool f = vr & (bool)((lv >> g) & 1u) & (r.cpu >= cpu[g]) & (r.mem >= mem[g]) & (r.gpu >= gpu[g]);
                     if (!f && ra[g] >= 0) {
                         if (s0 - ra[g] >= d[g]) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
                             atomicAdd(&ld[g][ra[g]], 1);
@@ -163,20 +163,10 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
                     }
                     if (f && ra[g] < 0 && s0 < H) ra[g] = s0;
                 }
-                s0 = min(max(e, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
+                s0 = min(max(r.end, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
             };
-#pragma unroll
-            for (int i = 0; i < TL_HEAD; ++i)
-                if (i < cn) step(true, h.head[i].cpu, h.head[i].mem, h.head[i].gpu, h.head[i].end);
-            for (int i = TL_HEAD; i < cn; i += 4) {  // four Seg per wait, as when_node
-                Seg r4[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (i + k < cn) step(true, r4[k].cpu, r4[k].mem, r4[k].gpu, r4[k].end);
-            }
-            step(false, 0, 0, 0, H);
+            tl_each_run(h, sg, cn, step);
+            step(Seg{H, 0, 0, 0}, false);
 #pragma unroll
             for (int g = 0; g < WK_GROUP; ++g) hosts[g] += (any >> g) & 1u;
         }
@@ -213,31 +203,11 @@ __global__ __launch_bounds__(256) void k_whenk_pick(const int32_t* __restrict__ 
     if (q < 0 || jcomp[q] < 0) return;  // rejected, or no member at all: start stays -1
     const int32_t need = out[q].need, d = out[q].dur;
     if (d > H) return;
-    const int32_t* df = diff + (int64_t)t * (H + 1);
-    int32_t carry = 0, start = -1, ready = 0, now = 0;
-    for (int base = 0; base < H; base += 64) {  // starts lie in [0, H - d]; word H only takes -1s
-        const int s = base + lane;
-        int32_t v = s < H ? df[s] : 0;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t u = __shfl_up(v, off);
-            if (lane >= off) v += u;
-        }
-        v += carry;  // cnt(s)
-        if (base == 0) now = __shfl(v, 0);
-        const uint64_t hit = __ballot(s < H && v >= need);
-        if (hit) {
-            const int first = __builtin_ctzll(hit);
-            start = base + first;
-            ready = __shfl(v, first);
-            break;
-        }
-        carry = __shfl(v, 63);
-    }
+    const TlStart f = tl_first_start(diff + (int64_t)t * (H + 1), H, need, lane);
     if (lane == 0) {
-        out[q].now = now;
-        out[q].start = start;
-        out[q].ready = ready;
+        out[q].now = f.now;
+        out[q].start = f.start;
+        out[q].ready = f.ready;
     }
 }
 
@@ -267,37 +237,9 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_nodes(
         if (!(h.mask & pbit) || cpu > h.cpu || mem > h.mem || gpu > h.gpu) continue;
         const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
         const int cn = min(h.cnt, TL_MAX_SLOTS);
-        int32_t mc = 0x7fffffff, mm = 0x7fffffff, mg = 0x7fffffff;
-        bool ok = true, closed = false;  // closed: the runs seen cover the window
-        // runs end in increasing order and the walk stops at the first that reaches `stop`, so a run
-        // meets the window exactly when it ends behind `start`
-        auto run = [&](const Seg& r) {
-            if (r.end <= start) return;
-            ok = (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
-            mc = min(mc, r.cpu);
-            mm = min(mm, r.mem);
-            mg = min(mg, r.gpu);
-            closed = r.end >= stop;
-        };
-#pragma unroll
-        for (int i = 0; i < TL_HEAD; ++i)
-            if (i < cn && ok && !closed) run(h.head[i]);
-        for (int i = TL_HEAD; i < cn && ok && !closed; i += 4) {  // four Seg per wait, as when_node
-            Seg r4[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) r4[k] = sg[i + k];  // inside the slab row (4 | TL_MAX_SLOTS)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (i + k < cn && ok && !closed) run(r4[k]);
-        }
-        if (!ok || !closed) continue;
-        uint64_t k = tl_key(0, mc, mm, mg, cpu, mem, gpu, (uint32_t)x);
-#pragma unroll
-        for (int i = 0; i < WHENK_KEYS; ++i) {  // sorted insert: k carries the larger one on
-            const uint64_t lo = min(k, key[i]);
-            k = max(k, key[i]);
-            key[i] = lo;
-        }
+        TL_WINDOW(h, sg, cn, start, stop, cpu, mem, gpu, mc, mm, mg, fits)
+        if (!fits) continue;
+        tl_keep(key, tl_key(0, mc, mm, mg, cpu, mem, gpu, (uint32_t)x));
     }
     // the workgroup's `need` smallest: per round the minimum of the threads' heads; keys are
     // distinct (the position), so exactly one thread owns it and moves its list up

@@ -74,6 +74,37 @@ def test_busy_cases_are_contended(H, j, kmax):
         assert runs.max() >= 17
 
 
+def test_busy_case_drives_every_run_list_length_and_both_node_paths():
+    """("busy", 64, 300, 8), which the GPU test runs as well: (a) its starting run lists have every
+    length the visit of a list distinguishes — header only, the header's edge, the four-run loads'
+    edges — and (b), (c) its placed jobs take both ways to the node list: some start later than a
+    node that is free at slot 0 (the window [start, start + d) is evaluated again), some start at 0
+    (the count walk's keys are the answer).  The reference gives run counts 1 .. 11 and 13 .. 17, and
+    of 287 placed jobs 60 of kind (b) and 92 of kind (c)."""
+    H, j, kmax = 64, 300, 8
+    nodes, tline, parts = pk.cluster(H)
+    jobs, out, start, fin = pk.reference("busy", H, j, kmax)
+    rc = wk.run_counts(pk.start_timeline(H)[nodes.part_mask != 0])
+    assert {1, 4, 5, 8, 9} <= set(rc.tolist()) and rc.max() >= 13, sorted(set(rc.tolist()))
+    # the replay: `now` of every job on the timeline as the jobs before it left it
+    tl = np.array(pk.start_timeline(H), np.int32, copy=True)
+    now = np.zeros(j, np.int32)
+    for q in range(j):
+        one = wk.one_job(jobs, q)
+        rows, sel = wk.ref_when_k(tl, nodes.part_mask, parts, one, pk.SLOT_MIN, kmax)
+        now[q] = rows["now"][0]
+        assert rows["start"][0] == start[q] or start[q] < 0
+        if start[q] >= 0:
+            need, d = int(rows["need"][0]), int(rows["dur"][0])
+            assert np.array_equal(sel[0, :need], out[q, :need])
+            tl[sel[0, :need], start[q]:start[q] + d] -= np.array([one.cpu[0], one.mem[0], one.gpu[0]], np.int32)
+    assert np.array_equal(tl, fin)
+    later_with_early, at_zero = (start > 0) & (now > 0), start == 0
+    print(f"run counts {sorted(set(rc.tolist()))} placed {(start >= 0).sum()} start > 0 and now > 0 "
+          f"{later_with_early.sum()} start == 0 {at_zero.sum()}")
+    assert later_with_early.any() and at_zero.any()
+
+
 def test_stairs_are_long_and_contended():
     nodes, tline, parts = pk.stairs()
     jobs, tl0, out, start, fin = pk.stairs_reference()
