@@ -784,6 +784,63 @@ int fit_preempt_k_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_preempt_k_message(const fit_evict_k* r, char* buf, int32_t buflen);
 
+/* ---- which running jobs to evict so that a job starts now ON THE TIMELINE ----
+ * fit_preempt for a caller who keeps the loaded timeline: the node table does not see the
+ * reservations that backfill committed, and a victim that ends at slot 3 frees nothing at slot 5,
+ * where a reservation of a higher-priority pending job sits.
+ *
+ * fit_load_victims_tl: fit_load_victims' CSR with one more column.  vic_end[k] is the slot at which
+ * the running job hands its resources back anyway (its release slot in fit_load_timeline's release
+ * events), 0 <= end <= H, H the loaded horizon.  Evicting the entry adds its amounts to the slots
+ * [0, end) of its node — what fit_unplace_tl with start 0 and wall end * slot_min does; an entry
+ * with end 0 frees nothing and keeps its place in the list.  vic_off NULL = every list is empty.
+ * These lists are independent of fit_load_victims': fit_load_nodes and fit_load_timeline drop them,
+ * fit_place_tl(_k), fit_unplace_tl and fit_hold_tl leave them alone, and fit_advance_tl(a) keeps them:
+ * from then on every end reads as max(end - a, 0) (the shifts add up, at most H; a new
+ * fit_load_victims_tl starts from 0 again).  FIT_E_INVAL: fit_load_victims' list, or an end outside
+ * [0, H]; the call then fails as a whole and the lists loaded before stay in place.  FIT_E_STATE:
+ * before fit_load_nodes; without a timeline; on a context created with world > 1 or
+ * FIT_FLAG_COLLECTIVES. */
+int fit_load_victims_tl(fit_ctx* ctx, const int32_t* vic_off /* n + 1 */, const int32_t* vic_prio,
+                        const int32_t* vic_end, const int32_t* vic_cpu, const int32_t* vic_mem,
+                        const int32_t* vic_gpu);
+/* Same with device pointers, validated by a kernel; n_vic as fit_load_victims_device's. */
+int fit_load_victims_tl_device(fit_ctx* ctx, const int32_t* vic_off, int64_t n_vic, const int32_t* vic_prio,
+                               const int32_t* vic_end, const int32_t* vic_cpu, const int32_t* vic_mem,
+                               const int32_t* vic_gpu);
+
+/* fit_preempt_tl judges each of J one-node jobs ALONE against the current timeline — what
+ * fit_read_timeline returns, reservations included — and the lists of fit_load_victims_tl, for a
+ * start NOW: the window [0, d), d = max(1, ceil(wall / slot_min)).  Nothing is written.  The rows,
+ * the codes with their precedence and fit_preempt_message are fit_preempt's; what changes is the
+ * rule per node:
+ *   Node n is ELIGIBLE when the job's partition bit is set in its mask, d <= H and every slot of
+ *   [0, d) reads >= 0 in all three columns (a -1 slot is closed and no eviction opens it).
+ *   L(n)      = the number of n's entries with priority STRICTLY BELOW the job's.
+ *   E_c(v, t) = the exact sum of column c over those of the first v entries whose end is > t.
+ *   v(n)      = the smallest v in [0, L(n)] with free_c(n, t) + E_c(v, t) >= demand_c for every t in
+ *               [0, d) and every column c.
+ * members, fit (v = 0), able (v >= 1) and outranked (no v in [0, L], some v in (L, list length]) count
+ * the nodes as fit_preempt does.  The node: with fit > 0 the smallest (score, node id) among the
+ * fitting nodes, the score of the window minima minus the demand — fit_when's node; victims =
+ * top_prio = 0.  Else with able > 0 the smallest (top, v, score, node id), top the priority of entry
+ * v - 1 and score that of min over t in [0, d) of min(free_c(t) + E_c(v, t), INT32_MAX) - demand_c.
+ * Else node = -1.  Not judged here: multi-node jobs, a start later than slot 0, sparing a victim of
+ * the prefix; nothing is evicted.
+ * Host pointers.  j == 0 returns 0 whatever the pointers are.  FIT_E_INVAL: as fit_preempt.
+ * FIT_E_STATE: before fit_load_nodes; without a timeline; before any fit_load_victims_tl since the
+ * timeline was loaded; on a context created with world > 1 or FIT_FLAG_COLLECTIVES.  Bounded
+ * launches (three per 16,384 jobs), no persistent grid: neither the per-GPU persistent-launch lock
+ * nor the watchdog. */
+int fit_preempt_tl(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const int32_t* prio, fit_evict* out);
+/* Same with device pointers (inputs resident in HBM, the rows written in HBM). */
+int fit_preempt_tl_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const int32_t* prio, fit_evict* out);
+/* Diagnostic, for measurement only (tools/preempt_tl_bench.py): device time of the last successful
+ * fit_preempt_tl_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
+int fit_preempt_tl_ms(fit_ctx* ctx, double* ms);
+
 /* ---- free capacity of every partition at every timeline slot ---------------
  * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
  * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced

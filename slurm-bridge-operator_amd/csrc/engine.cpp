@@ -366,6 +366,16 @@ struct fit_ctx : CtxHandles {
     QueryBufs<fit_evict_k> pk;
     DBuf<int32_t> pk_node, pk_vic;
     HBuf<int32_t> h_pk_pick;
+    // fit_load_victims_tl / fit_preempt_tl: the victims of the loaded timeline
+    // in position order, their own buffers and flag (vtl_off: nn + 1 offsets; vtl_ent: priority, end
+    // slot, raw amounts), the slots fit_advance_tl has moved the timeline by since they were loaded,
+    // and the query's rows.  The staged CSR (vs_*, vic_bad), the staged priorities and the key scratch
+    // are fit_load_victims' and fit_preempt's: every call ends synchronised on the one stream.
+    DBuf<int32_t> vs_end, vtl_off;
+    DBuf<VicTl> vtl_ent;
+    bool have_vtl = false;
+    int32_t vtl_shift = 0;
+    QueryBufs<fit_evict> pt;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1556,6 +1566,56 @@ int check_victims_state(fit_ctx* c) {
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_preempt_tl
+// fit_preempt's sequence, classifier, slices, partials and final kernel; the
+// walk reads the run lists and the timeline's own victims.
+int preempt_tl_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio, fit_evict* out, int32_t* bad) {
+    const int S = preempt_slices(J, c->cls_maxn, c->cus);
+    if (c->pe_part.ensure(preempt_partials(J, S))) return FIT_E_OOM;
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_preempt_classify(c->st, c->d_ptab.p, c->np, c->ncomp, d.cpu, d.mem, d.gpu, d.wall, d.part, J,
+                                           out, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_preempt_tl(c->st, c->tlhdr.p, c->slab.p, c->vtl_off.p, c->vtl_ent.p, ec, c->tl_slots,
+                                     c->tl_slot_min, c->vtl_shift, d.cpu, d.mem, d.gpu, d.wall, d.part, prio, J,
+                                     c->jcomp.p, jl, live, S, c->pe_part.p, out);
+        });
+}
+
+// fit_load_victims_tl / fit_load_victims_tl_device behind their checks, as load_victims_impl: the
+// position-ordered offsets from the caller's (h_off: host copy, nullptr = every list empty), then the
+// entries from the device CSR.  The lists loaded before are replaced from the first write on.
+int load_victims_tl_impl(fit_ctx* c, const int32_t* h_off, const int32_t* off, const int32_t* prio, const int32_t* end,
+                         const int32_t* cpu, const int32_t* mem, const int32_t* gpu) {
+    std::vector<int32_t> hv((size_t)c->nn + 1, 0);
+    if (h_off)
+        for (int32_t i = 0; i < c->nn; ++i) {
+            const int32_t x = c->h_perm[i];
+            hv[i + 1] = hv[i] + (h_off[x + 1] - h_off[x]);
+        }
+    c->have_vtl = false;
+    if (c->vtl_off.ensure(hv.size()) || c->vtl_ent.ensure(std::max<int32_t>(hv[c->nn], 1))) return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->vtl_off.p, hv.data(), sizeof(int32_t) * hv.size(), hipMemcpyHostToDevice, c->st));
+    if (hv[c->nn] > 0)
+        HIP_TRY(launch_vtl_build(c->st, off, prio, end, cpu, mem, gpu, c->perm.p, c->nn, c->vtl_off.p, c->vtl_ent.p));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    c->vtl_shift = 0;
+    c->have_vtl = true;
+    return 0;
+}
+
+int check_victims_tl_state(fit_ctx* c) {
+    if (!c) return fail(FIT_E_INVAL, "null ctx");
+    if (!c->have_nodes) return fail(FIT_E_STATE, "fit_load_nodes not called");
+    if (c->collective())
+        return fail(FIT_E_STATE, "fit_load_victims_tl on a sharded context (world > 1 / FIT_FLAG_COLLECTIVES)");
+    if (!c->have_tl) return fail(FIT_E_STATE, "fit_load_timeline not called");
+    return 0;
+}
+
 // --------------------------------------------------------------------------- fit_when_k
 // classify the batch, (more than a group of jobs on several components: the
 // jobs in component order), then per chunk of WHENK_CHUNK jobs count (difference arrays), pick the
@@ -1819,6 +1879,8 @@ int advance_tl_impl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm,
         &ms);
     if (rc) return rc;
     c->atl_ms = ms;
+    // fit_preempt_tl reads every victim's end as max(end - shift, 0): no rewrite of the entries
+    c->vtl_shift = std::min(c->vtl_shift + std::min(a, c->tl_slots), c->tl_slots);
     return 0;
 }
 
@@ -1973,6 +2035,7 @@ int load_timeline_impl(fit_ctx* c, int32_t slots, int32_t slot_min, int64_t ne) 
         c->slab.ensure((size_t)std::max(c->nn, 1) * TL_MAX_SLOTS) || c->tl_err.ensure(1) ||
         c->h_tl_err.ensure(1))
         return FIT_E_OOM;
+    c->have_vtl = false;  // the victims' ends are slots of the timeline they were loaded for
     HIP_TRY(hipMemsetAsync(c->tl_err.p, 0, 4, c->st));
     HIP_TRY(launch_build_tl(c->st, c->col_cpu.p, c->col_mem.p, c->col_gpu.p, c->col_av.p,
                             c->col_mask.p, c->perm.p, c->nn, slots, slot_min, ne >= 0 ? c->rel_off.p : nullptr,
@@ -2160,7 +2223,7 @@ static int load_node_cols(fit_ctx* c, int32_t n, const int32_t* cpu, const int32
     // the columns are overwritten below: until the load succeeds there is no valid node table
     // (a failed load must not leave new offsets paired with old node rows)
     c->have_nodes = c->have_tl = false;
-    c->have_vic = false;  // the victims are lists by node id, and the ids change
+    c->have_vic = c->have_vtl = false;  // the victims are lists by node id, and the ids change
     HIP_TRY(hipSetDevice(c->device));
     if (alloc_cols(c, n)) return FIT_E_OOM;
     const size_t b = sizeof(int32_t) * n;
@@ -2551,6 +2614,119 @@ int fit_preempt_k_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->pk.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_k_device yet");
     *ms = c->pk.ms;
+    return 0;
+}
+
+// fit_load_victims_tl / fit_load_victims_tl_device: fit_load_victims' tests plus the end column
+int fit_load_victims_tl(fit_ctx* c, const int32_t* vic_off, const int32_t* vic_prio, const int32_t* vic_end,
+                        const int32_t* vic_cpu, const int32_t* vic_mem, const int32_t* vic_gpu) {
+    const int rc = check_victims_tl_state(c);
+    if (rc) return rc;
+    int64_t nv = 0;
+    if (vic_off) {  // everything is judged before anything is written: a bad list leaves the loaded lists
+        if (vic_off[0] != 0) return fail(FIT_E_INVAL, "vic_off[0] must be 0");
+        for (int32_t x = 0; x < c->n; ++x)
+            if (vic_off[x + 1] < vic_off[x]) return fail(FIT_E_INVAL, "vic_off decreases at %d", x);
+        nv = vic_off[c->n];
+        if (nv > 0 && (!vic_prio || !vic_end || !vic_cpu || !vic_mem || !vic_gpu))
+            return fail(FIT_E_INVAL, "null victim arrays");
+        for (int32_t x = 0; x < c->n; ++x)
+            for (int32_t k = vic_off[x]; k < vic_off[x + 1]; ++k) {
+                if (vic_cpu[k] < 0 || vic_mem[k] < 0 || vic_gpu[k] < 0)
+                    return fail(FIT_E_INVAL, "victim %d of node %d holds a negative amount", k - vic_off[x], x);
+                if (vic_end[k] < 0 || vic_end[k] > c->tl_slots)
+                    return fail(FIT_E_INVAL, "victim %d of node %d ends at slot %d (0..%d)", k - vic_off[x], x,
+                                vic_end[k], c->tl_slots);
+                if (k > vic_off[x] && vic_prio[k] < vic_prio[k - 1])
+                    return fail(FIT_E_INVAL, "victims of node %d are not in eviction order (priority decreases at %d)",
+                                x, k - vic_off[x]);
+            }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (nv > 0) {
+        const size_t b = sizeof(int32_t) * nv, bo = sizeof(int32_t) * ((size_t)c->n + 1);
+        if (c->vs_off.ensure((size_t)c->n + 1) || c->vs_prio.ensure(nv) || c->vs_end.ensure(nv) ||
+            c->vs_cpu.ensure(nv) || c->vs_mem.ensure(nv) || c->vs_gpu.ensure(nv))
+            return FIT_E_OOM;
+        HIP_TRY(hipMemcpyAsync(c->vs_off.p, vic_off, bo, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_prio.p, vic_prio, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_end.p, vic_end, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_cpu.p, vic_cpu, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_mem.p, vic_mem, b, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->vs_gpu.p, vic_gpu, b, hipMemcpyHostToDevice, c->st));
+    }
+    return load_victims_tl_impl(c, nv > 0 ? vic_off : nullptr, c->vs_off.p, c->vs_prio.p, c->vs_end.p, c->vs_cpu.p,
+                                c->vs_mem.p, c->vs_gpu.p);
+}
+
+int fit_load_victims_tl_device(fit_ctx* c, const int32_t* vic_off, int64_t n_vic, const int32_t* vic_prio,
+                               const int32_t* vic_end, const int32_t* vic_cpu, const int32_t* vic_mem,
+                               const int32_t* vic_gpu) {
+    const int rc = check_victims_tl_state(c);
+    if (rc) return rc;
+    if (n_vic < 0 || n_vic > INT32_MAX ||
+        (n_vic > 0 && (!vic_off || !vic_prio || !vic_end || !vic_cpu || !vic_mem || !vic_gpu)))
+        return fail(FIT_E_INVAL, "bad victim arrays");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!vic_off) return load_victims_tl_impl(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    // judged by a kernel, the offsets come to the host for the position order; the loaded lists stay
+    // untouched until the verdict is in
+    if (c->vic_bad.ensure(1) || c->h_vic_bad.ensure(1)) return FIT_E_OOM;
+    std::vector<int32_t> h_off((size_t)c->n + 1);
+    HIP_TRY(hipMemsetAsync(c->vic_bad.p, 0, sizeof(int32_t), c->st));
+    HIP_TRY(launch_vtl_check(c->st, vic_off, c->n, n_vic, vic_prio, vic_end, vic_cpu, vic_mem, vic_gpu, c->tl_slots,
+                             c->vic_bad.p));
+    HIP_TRY(hipMemcpyAsync(c->h_vic_bad.p, c->vic_bad.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(h_off.data(), vic_off, sizeof(int32_t) * h_off.size(), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->h_vic_bad.p[0])
+        return fail(FIT_E_INVAL, "victims: vic_off must start at 0, not decrease and end at n_vic; amounts >= 0; "
+                                 "ends in [0, %d]; priorities non-decreasing inside a node", c->tl_slots);
+    return load_victims_tl_impl(c, n_vic > 0 ? h_off.data() : nullptr, vic_off, vic_prio, vic_end, vic_cpu, vic_mem,
+                                vic_gpu);
+}
+
+// fit_preempt_tl / fit_preempt_tl_device: fit_when's tests, then the timeline's victims
+static int check_preempt_tl_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays) {
+    const int rc = check_job_args(c, j, arrays, "fit_preempt_tl", 1);
+    if (rc) return rc;
+    if (!c->have_vtl) return fail(FIT_E_STATE, "fit_load_victims_tl not called");
+    return 0;
+}
+
+int fit_preempt_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const int32_t* prio, fit_evict* out) {
+    const int rc = check_preempt_tl_args(c, j, {cpu, mem, gpu, wall, part, prio, out});
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the priorities ride beside the packed columns, as fit_preempt's
+    if (c->pe_prio.ensure(j) || c->h_pe_prio.ensure(j)) return FIT_E_OOM;
+    memcpy(c->h_pe_prio.p, prio, sizeof(int32_t) * j);
+    HIP_TRY(hipMemcpyAsync(c->pe_prio.p, c->h_pe_prio.p, sizeof(int32_t) * j, hipMemcpyHostToDevice, c->st));
+    return query_host(
+        c, c->pt, j, cpu, mem, gpu, wall, part, nullptr, out,
+        [](fit_ctx* x, int32_t n, const JobCols& d, fit_evict* rows, int32_t* bad) {
+            return preempt_tl_impl(x, n, d, x->pe_prio.p, rows, bad);
+        },
+        bad_room_job);
+}
+
+int fit_preempt_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const int32_t* prio, fit_evict* out) {
+    const int rc = check_preempt_tl_args(c, j, {cpu, mem, gpu, wall, part, prio, out});
+    if (rc || j == 0) return rc;
+    return query_device(
+        c, c->pt, j, {cpu, mem, gpu, wall, part, nullptr}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict* rows, int32_t* bad) {
+            return preempt_tl_impl(x, n, d, prio, rows, bad);
+        },
+        bad_room_job);
+}
+
+int fit_preempt_tl_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->pt.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_tl_device yet");
+    *ms = c->pt.ms;
     return 0;
 }
 

@@ -390,6 +390,30 @@ hipError_t launch_preempt_k(hipStream_t st, const NodeRec* rec, const int32_t* v
                             int32_t nj, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
                             void* part, void* out, int32_t* out_node, int32_t* out_vic);
 
+// ---- fit_load_victims_tl / fit_preempt_tl (fit_preempt_tl.hip) ---------
+// fit_preempt's codes, rows, classifier, slices, chunk and partials; the walk reads the run lists.
+// One victim of a node position, 32 B (one scalar s_load_dwordx8): its priority, the slot at which it
+// hands its resources back anyway and the raw amounts it holds
+struct alignas(32) VicTl {
+    int32_t prio, end, cpu, mem, gpu, pad[3];
+};
+// launch_vic_check's test plus 0 <= end <= H
+hipError_t launch_vtl_check(hipStream_t st, const int32_t* off, int32_t n, int64_t nvic, const int32_t* prio,
+                            const int32_t* end, const int32_t* cpu, const int32_t* mem, const int32_t* gpu, int32_t H,
+                            int32_t* bad);
+hipError_t launch_vtl_build(hipStream_t st, const int32_t* off, const int32_t* prio, const int32_t* end,
+                            const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* perm, int32_t nn,
+                            const int32_t* voff, VicTl* vent);
+// k_pre_final (fit_preempt.hip) for the positions [t0, t0 + nt) of a walk's partials
+hipError_t launch_preempt_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
+                                int32_t nt, int ncomp, int slices, const int8_t* jcomp, const void* part, void* out);
+// shift: the slots fit_advance_tl has moved the timeline by since the victims were loaded, in [0, H]
+hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff, const VicTl* vent,
+                             const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift, const int32_t* jcpu,
+                             const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
+                             const int32_t* jprio, int32_t nj, const int8_t* jcomp, const int32_t* jl,
+                             const int32_t* live, int slices, void* part, void* out);
+
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {
     TRIP_NONE = 0,

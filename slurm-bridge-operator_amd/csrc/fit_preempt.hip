@@ -248,6 +248,15 @@ hipError_t launch_preempt_classify(hipStream_t st, const int32_t* ptab, int32_t 
                           static_cast<EvictRow*>(out), jcomp, bad);
 }
 
+// k_pre_final for a walk of another file (fit_preempt_tl.hip): one chunk's positions [t0, t0 + nt)
+hipError_t launch_preempt_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
+                                int32_t nt, int ncomp, int slices, const int8_t* jcomp, const void* part, void* out) {
+    if (nt <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pre_final, dim3((nt + 255) / 256), dim3(256), 0, st, jl, live, nj, t0, nt, (int32_t)ncomp,
+                       slices, jcomp, static_cast<const PreKey*>(part), static_cast<EvictRow*>(out));
+    return hipGetLastError();
+}
+
 // Node slices of the walk and the partials it needs (16 bytes each) for a batch of nj jobs: a chunk's
 // positions x its slices, at most about 8 workgroups per CU x 64 jobs whatever nj is.
 int preempt_slices(int32_t nj, int32_t maxn, int cus) { return explain_slices(std::min(nj, PRE_CHUNK), maxn, cus); }

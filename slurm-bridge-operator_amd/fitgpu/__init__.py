@@ -925,6 +925,63 @@ class Engine:
         check(lib().fit_preempt_ms(self._h, C.byref(ms)), "fit_preempt_ms")
         return ms.value
 
+    # ---- which running jobs to evict so that a job starts now on the timeline --
+    def load_victims_tl(self, victims):
+        """The preemptible running jobs per node for the loaded timeline (fit_load_victims_tl):
+        load_victims' CSR plus `end`, the slot at which each job hands its resources back anyway
+        (0 <= end <= H) — or None: every list empty.  After load_timeline, which drops them;
+        advance_tl keeps them and moves their ends along."""
+        if victims is None:
+            check(lib().fit_load_victims_tl(self._h, None, None, None, None, None, None), "fit_load_victims_tl")
+            return
+        cols = [np.ascontiguousarray(getattr(victims, f), np.int32) for f in ("off", "prio", "end", "cpu", "mem", "gpu")]
+        if len(cols[0]) != self.n + 1 or any(len(c) != len(cols[1]) for c in cols[2:]) or (
+                len(cols[0]) and int(cols[0].max()) > len(cols[1])):
+            raise ValueError("victims: off must have n + 1 entries that index equally long columns")
+        check(lib().fit_load_victims_tl(self._h, *[_ptr(c) if len(c) else None for c in cols]), "fit_load_victims_tl")
+
+    def load_victims_tl_device(self, off, prio, end, cpu, mem, gpu):
+        """torch int32 tensors on this GPU (off has n + 1 entries, the others off[n]); off None: every
+        list empty.  The lists are validated by a kernel."""
+        if off is None:
+            check(lib().fit_load_victims_tl_device(self._h, None, 0, None, None, None, None, None),
+                  "fit_load_victims_tl_device")
+            return
+        check(lib().fit_load_victims_tl_device(self._h, _ptr(off), int(prio.numel()),
+                                               *[_ptr(t) if t.numel() else None for t in (prio, end, cpu, mem, gpu)]),
+              "fit_load_victims_tl_device")
+
+    def preempt_tl(self, jobs, prio):
+        """Every job judged alone, for a start now, against the current timeline (reservations
+        included) and the lists of load_victims_tl (fit_preempt_tl): EVICT_DTYPE rows, as preempt's.
+        Changes nothing; jobs.nodes_k plays no part (each job takes one node)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        prio = np.ascontiguousarray(prio, np.int32)
+        if len(prio) != len(part):
+            raise ValueError("prio must have one entry per job")
+        out = np.zeros(len(part), EVICT_DTYPE)
+        check(lib().fit_preempt_tl(self._h, len(part), *[_ptr(c) for c in cols], _ptr(part), _ptr(prio), _ptr(out)),
+              "fit_preempt_tl")
+        return out
+
+    def preempt_tl_device(self, cpu, mem, gpu, wall, part, prio, out):
+        """All arguments torch tensors resident on this GPU; writes out (J rows of 8 int32, the fields
+        of EVICT_DTYPE in order).  Returns the device time of its launches in ms (fit_preempt_tl_ms);
+        0.0 for no jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_preempt_tl_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                          _ptr(prio), _ptr(out)), "fit_preempt_tl_device")
+        if j == 0:
+            return 0.0
+        return self.preempt_tl_ms()
+
+    def preempt_tl_ms(self):
+        """Device time in ms of the last successful preempt_tl_device (fit_preempt_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_preempt_tl_ms(self._h, C.byref(ms)), "fit_preempt_tl_ms")
+        return ms.value
+
     # ---- which victims to evict so that a multi-node job fits (DESIGN.md §2m) -----------------
     def preempt_k(self, jobs, prio, kmax: int | None = None):
         """Every job judged alone against the current node table and the loaded victims, on

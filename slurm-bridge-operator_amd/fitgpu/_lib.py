@@ -52,6 +52,8 @@ EXPORTS = [
     "fit_load_victims", "fit_load_victims_device", "fit_preempt", "fit_preempt_device", "fit_preempt_ms",
     "fit_preempt_message",
     "fit_preempt_k", "fit_preempt_k_device", "fit_preempt_k_ms", "fit_preempt_k_message",
+    "fit_load_victims_tl", "fit_load_victims_tl_device", "fit_preempt_tl", "fit_preempt_tl_device",
+    "fit_preempt_tl_ms",
 ]
 
 
@@ -242,6 +244,11 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P, i32, P, P, P]
         L.fit_preempt_k_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_preempt_k_message.argtypes = [C.POINTER(FitEvictK), C.c_char_p, i32]
+        L.fit_load_victims_tl.argtypes = [P, P, P, P, P, P, P]
+        L.fit_load_victims_tl_device.argtypes = [P, P, i64, P, P, P, P, P]
+        for name in ("fit_preempt_tl", "fit_preempt_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P]
+        L.fit_preempt_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

@@ -338,6 +338,45 @@ def pack_victims(seed: int, nodes: Nodes, cpus=VIC_CPUS, empty_pm: int = VIC_EMP
                            held[1][valid].astype(np.int32), held[2][valid].astype(np.int32))
 
 
+S_VEND = 46
+
+
+@dataclass
+class VictimsTL:
+    """Victims for a loaded timeline (fit_load_victims_tl): Victims plus `end`, the slot
+    at which each running job hands its resources back anyway, 0 <= end <= slots."""
+    off: np.ndarray   # int32 [n + 1]
+    prio: np.ndarray  # int32 [V]
+    end: np.ndarray   # int32 [V]
+    cpu: np.ndarray   # int32 [V]
+    mem: np.ndarray   # int32 [V], MiB
+    gpu: np.ndarray   # int32 [V]
+
+
+def gen_victim_ends(seed: int, victims: Victims, slots: int, slot_min: int, ends=None) -> tuple[VictimsTL, Timeline]:
+    """pack_victims' output with ends, and the release events that match them: every victim ends at a
+    slot drawn from `ends` (default: uniform in [1, slots]), and hands back what it holds there.  The
+    events are sorted by slot inside a node, as fit_load_timeline wants them; a victim that ends at
+    `slots` outlives the horizon and has no event.  A timeline loaded from the packed node table and
+    these events is what the cluster looks like when nothing is evicted."""
+    k = np.arange(len(victims.prio), dtype=np.uint64)
+    if ends is None:
+        end = 1 + uni(rnd(seed, S_VEND, k), slots)
+    else:
+        ends = np.asarray(ends, np.int64)
+        end = ends[uni(rnd(seed, S_VEND, k), len(ends))]
+    end = end.astype(np.int32)
+    n = len(victims.off) - 1
+    node = np.repeat(np.arange(n), np.diff(victims.off))
+    order = np.lexsort((end, node))  # by node, then slot; stable among equal slots
+    order = order[end[order] < slots]
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(node[order], minlength=n))
+    tline = Timeline(slots, slot_min, off.astype(np.int32), end[order], victims.cpu[order].astype(np.int32),
+                     victims.mem[order].astype(np.int32), victims.gpu[order].astype(np.int32))
+    return VictimsTL(victims.off, victims.prio, end, victims.cpu, victims.mem, victims.gpu), tline
+
+
 def gen_job_prio(seed: int, j: int, start: int = 0) -> np.ndarray:
     """Priorities of the pending jobs [start, start + j), from JOB_PRIO."""
     i = np.arange(start, start + j, dtype=np.uint64)

@@ -805,6 +805,66 @@ func PreemptKMessage(r EvictK) string {
 	return string(buf[:int(n)])
 }
 
+// VictimsTL are Victims for a loaded timeline (DESIGN.md §2n): End[k] is the slot at which the
+// running job hands its resources back anyway, 0 <= End <= the horizon.  Evicting the entry frees
+// what it holds on the slots [0, End) of its node.
+type VictimsTL struct {
+	Off, Prio, End, CPU, MemMiB, GPU []int32
+}
+
+// LoadVictimsTL hands the engine the running jobs PreemptTL may evict (fit_load_victims_tl), after
+// LoadTimeline, which drops them; AdvanceTL keeps them and moves their ends along.  An empty Off
+// means no node has a victim.
+func (e *Engine) LoadVictimsTL(v VictimsTL) error {
+	if !sameLen(len(v.Prio), len(v.End), len(v.CPU), len(v.MemMiB), len(v.GPU)) {
+		return errLen
+	}
+	if len(v.Off) == 0 {
+		err := check(C.fit_load_victims_tl(e.ctx, nil, nil, nil, nil, nil, nil))
+		runtime.KeepAlive(e)
+		return err
+	}
+	if int(v.Off[len(v.Off)-1]) > len(v.Prio) {
+		return fmt.Errorf("fitgpu: Off ends at %d but there are %d victims", v.Off[len(v.Off)-1], len(v.Prio))
+	}
+	var p, d, c, m, g *C.int32_t
+	if len(v.Prio) > 0 {
+		p, d = (*C.int32_t)(unsafe.Pointer(&v.Prio[0])), (*C.int32_t)(unsafe.Pointer(&v.End[0]))
+		c, m = (*C.int32_t)(unsafe.Pointer(&v.CPU[0])), (*C.int32_t)(unsafe.Pointer(&v.MemMiB[0]))
+		g = (*C.int32_t)(unsafe.Pointer(&v.GPU[0]))
+	}
+	err := check(C.fit_load_victims_tl(e.ctx, (*C.int32_t)(unsafe.Pointer(&v.Off[0])), p, d, c, m, g))
+	runtime.KeepAlive(e)
+	return err
+}
+
+// PreemptTL is Preempt on the loaded timeline (fit_preempt_tl): every job judged alone, for a start
+// now, against the current timeline — reservations included — and the victims of LoadVictimsTL.  The
+// rows are Preempt's, PreemptMessage gives their text.  It changes nothing and evicts nothing.
+func (e *Engine) PreemptTL(j Jobs, prio []int32) ([]Evict, error) {
+	cnt := len(j.CPU)
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part), len(prio)) {
+		return nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil
+	}
+	rows := make([]C.fit_evict, cnt)
+	rc := C.fit_preempt_tl(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])),
+		(*C.int32_t)(unsafe.Pointer(&prio[0])), &rows[0])
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, err
+	}
+	out := make([]Evict, cnt)
+	for i := range rows {
+		out[i] = goEvict(&rows[i])
+	}
+	return out, nil
+}
+
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
 // nodes that are open there (DESIGN.md §2k).
 type Free struct {
