@@ -841,6 +841,35 @@ int fit_preempt_tl_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int
  * fit_preempt_tl_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
 int fit_preempt_tl_ms(fit_ctx* ctx, double* ms);
 
+/* ---- victims for a MULTI-NODE job on the timeline ----------------------------
+ * fit_preempt_tl for a job that needs need = max(nodes_k, 1) distinct nodes at once, 1 <= need <= kmax
+ * <= FIT_MAX_K, all of them from slot 0: the common window is [0, d).  The state is fit_preempt_tl's,
+ * unchanged — the loaded timeline, the lists of fit_load_victims_tl with their ends, the shift of
+ * fit_advance_tl; the row, the codes with their precedence, the picks and the text are
+ * fit_preempt_k's (fit_evict_k, fit_preempt_k_message).  Each job is judged alone and nothing is
+ * written.  Per node, eligibility, L(n), E_c(v, t), v(n) and the counters are fit_preempt_tl's; every
+ * eligible node with some v(n) in [0, L(n)] has the key (top, v, score, node id), the score that of
+ * min over t in [0, d) of min(free_c(t) + E_c(v, t), INT32_MAX) - demand_c, and a node that fits now
+ * (v = 0) first word 0.  A job has picks when fit + able >= need: the `need` smallest keys, in key
+ * order, in out_node / out_victims as fit_preempt_k's — the caller evicts the first out_victims
+ * entries of each pick's list.  With need == 1 the row and entry 0 of the two arrays are
+ * fit_preempt_tl's row, field for field; a FITS row lists the nodes fit_when_k lists.
+ * Host pointers; nodes_k NULL = every job needs one node.  j == 0 returns 0 once the state and kmax
+ * have been judged.  FIT_E_INVAL: as fit_preempt_k.  FIT_E_STATE: as fit_preempt_tl.  Bounded launches
+ * (three per 16,384 jobs), no persistent grid: neither the per-GPU persistent-launch lock nor the
+ * watchdog. */
+int fit_preempt_tl_k(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                     const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k /* NULL = all 1 */,
+                     const int32_t* prio, int32_t kmax, fit_evict_k* out, int32_t* out_node /* j*kmax */,
+                     int32_t* out_victims /* j*kmax */);
+/* Same with device pointers (inputs resident in HBM, the rows and the picks written in HBM). */
+int fit_preempt_tl_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                            const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, const int32_t* prio,
+                            int32_t kmax, fit_evict_k* out, int32_t* out_node, int32_t* out_victims);
+/* Diagnostic, for measurement only (tools/preempt_tl_k_bench.py): device time of the last successful
+ * fit_preempt_tl_k_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
+int fit_preempt_tl_k_ms(fit_ctx* ctx, double* ms);
+
 /* ---- free capacity of every partition at every timeline slot ---------------
  * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
  * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced

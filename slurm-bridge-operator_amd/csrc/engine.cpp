@@ -376,6 +376,9 @@ struct fit_ctx : CtxHandles {
     bool have_vtl = false;
     int32_t vtl_shift = 0;
     QueryBufs<fit_evict> pt;
+    // fit_preempt_tl_k: its rows.  The victims and the shift are fit_preempt_tl's,
+    // the staged priorities, the key scratch and the picks' buffers fit_preempt_k's.
+    QueryBufs<fit_evict_k> ptk;
     int cus = 256;
     DBuf<uint8_t> ectl, ering;
     DBuf<CompState> ecs;
@@ -1585,6 +1588,26 @@ int preempt_tl_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio
         });
 }
 
+// --------------------------------------------------------------------------- fit_preempt_tl_k
+// fit_preempt_k's sequence, classifier, slices, lists and final kernel; the
+// walk reads the run lists and the timeline's own victims, as fit_preempt_tl's.
+int preempt_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio, int32_t kmax, fit_evict_k* out,
+                      int32_t* out_node, int32_t* out_vic, int32_t* bad) {
+    const int S = preempt_slices(J, c->cls_maxn, c->cus);
+    if (c->pe_part.ensure(preempt_k_partials(J, S, kmax))) return FIT_E_OOM;
+    return query_impl(
+        c, J, bad,
+        [&] {
+            return launch_preempt_k_classify(c->st, c->d_ptab.p, c->np, c->ncomp, d.cpu, d.mem, d.gpu, d.wall, d.part,
+                                             d.nk, kmax, J, out, out_node, out_vic, c->jcomp.p, bad);
+        },
+        [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
+            return launch_preempt_tl_k(c->st, c->tlhdr.p, c->slab.p, c->vtl_off.p, c->vtl_ent.p, ec, c->tl_slots,
+                                       c->tl_slot_min, c->vtl_shift, d.cpu, d.mem, d.gpu, d.wall, d.part, prio, kmax,
+                                       J, c->jcomp.p, jl, live, S, c->pe_part.p, out, out_node, out_vic);
+        });
+}
+
 // fit_load_victims_tl / fit_load_victims_tl_device behind their checks, as load_victims_impl: the
 // position-ordered offsets from the caller's (h_off: host copy, nullptr = every list empty), then the
 // entries from the device CSR.  The lists loaded before are replaced from the first write on.
@@ -2727,6 +2750,67 @@ int fit_preempt_tl_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->pt.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_tl_device yet");
     *ms = c->pt.ms;
+    return 0;
+}
+
+// fit_preempt_tl_k / fit_preempt_tl_k_device: fit_preempt_tl's tests, then kmax (nodes_k against kmax is
+// the device's flag word)
+static int check_preempt_tl_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
+    const int rc = check_job_args(c, j, arrays, "fit_preempt_tl_k", 1);
+    if (rc) return rc;
+    if (!c->have_vtl) return fail(FIT_E_STATE, "fit_load_victims_tl not called");
+    if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
+    return 0;
+}
+
+int fit_preempt_tl_k(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                     const int32_t* wall, const uint16_t* part, const uint16_t* nk, const int32_t* prio, int32_t kmax,
+                     fit_evict_k* out, int32_t* out_node, int32_t* out_victims) {
+    const int rc = check_preempt_tl_k_args(c, j, {cpu, mem, gpu, wall, part, prio, out, out_node, out_victims}, kmax);
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the priorities and the picks as fit_preempt_k's: staged beside the packed columns, back into
+    // pinned memory behind the launches, handed to the caller only when the call succeeds
+    const size_t nn = (size_t)j * kmax;
+    if (c->pe_prio.ensure(j) || c->h_pe_prio.ensure(j) || c->pk_node.ensure(nn) || c->pk_vic.ensure(nn) ||
+        c->h_pk_pick.ensure(2 * nn))
+        return FIT_E_OOM;
+    memcpy(c->h_pe_prio.p, prio, sizeof(int32_t) * j);
+    HIP_TRY(hipMemcpyAsync(c->pe_prio.p, c->h_pe_prio.p, sizeof(int32_t) * j, hipMemcpyHostToDevice, c->st));
+    const int r = query_host(
+        c, c->ptk, j, cpu, mem, gpu, wall, part, nk, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict_k* rows, int32_t* bad) {
+            const int e = preempt_tl_k_impl(x, n, d, x->pe_prio.p, kmax, rows, x->pk_node.p, x->pk_vic.p, bad);
+            if (e) return e;
+            HIP_TRY(hipMemcpyAsync(x->h_pk_pick.p, x->pk_node.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, x->st));
+            HIP_TRY(hipMemcpyAsync(x->h_pk_pick.p + nn, x->pk_vic.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost,
+                                   x->st));
+            return 0;
+        },
+        bad_when_k_job);
+    if (r) return r;
+    memcpy(out_node, c->h_pk_pick.p, sizeof(int32_t) * nn);
+    memcpy(out_victims, c->h_pk_pick.p + nn, sizeof(int32_t) * nn);
+    return 0;
+}
+
+int fit_preempt_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                            const int32_t* wall, const uint16_t* part, const uint16_t* nk, const int32_t* prio,
+                            int32_t kmax, fit_evict_k* out, int32_t* out_node, int32_t* out_victims) {
+    const int rc = check_preempt_tl_k_args(c, j, {cpu, mem, gpu, wall, part, prio, out, out_node, out_victims}, kmax);
+    if (rc || j == 0) return rc;
+    return query_device(
+        c, c->ptk, j, {cpu, mem, gpu, wall, part, nk}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_evict_k* rows, int32_t* bad) {
+            return preempt_tl_k_impl(x, n, d, prio, kmax, rows, out_node, out_victims, bad);
+        },
+        bad_when_k_job);
+}
+
+int fit_preempt_tl_k_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->ptk.ms < 0) return fail(FIT_E_STATE, "no fit_preempt_tl_k_device yet");
+    *ms = c->ptk.ms;
     return 0;
 }
 

@@ -414,6 +414,19 @@ hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, 
                              const int32_t* jprio, int32_t nj, const int8_t* jcomp, const int32_t* jl,
                              const int32_t* live, int slices, void* part, void* out);
 
+// ---- fit_preempt_tl_k (fit_preempt_tl_k.hip) ----------------------------
+// fit_preempt_tl's state and walk frame with fit_preempt_k's rows, classifier, lists and final kernel.
+// k_prek_final (fit_preempt_k.hip) for the positions [t0, t0 + nt) of a walk's lists of kmax keys
+hipError_t launch_preempt_k_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
+                                  int32_t nt, int ncomp, int slices, int32_t kmax, const int8_t* jcomp,
+                                  const void* part, void* out, int32_t* out_node, int32_t* out_vic);
+hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff,
+                               const VicTl* vent, const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift,
+                               const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                               const uint16_t* jpart, const int32_t* jprio, int32_t kmax, int32_t nj,
+                               const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* part,
+                               void* out, int32_t* out_node, int32_t* out_vic);
+
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {
     TRIP_NONE = 0,

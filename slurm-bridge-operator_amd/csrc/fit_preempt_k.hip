@@ -26,61 +26,14 @@
 
 #include "fit_device.h"
 #include "fit_pre_row.h"
+#include "fit_pre_top.h"
 #include "fit_query.h"
 
 namespace fitgpu {
 
-// fit_evict_k as the kernels see it (include/fitgpu.h)
-struct alignas(8) EvictKRow {
-    int32_t code, need, evict_nodes, victims, top_prio, cnt[PRE_NCNT], reserved;
-};
-static_assert(sizeof(EvictKRow) == 40 && offsetof(EvictKRow, cnt) == 20, "fit_evict_k is 40 bytes, its counters at 20");
-
-__device__ __forceinline__ bool prek_less(uint64_t ahi, uint64_t alo, uint64_t bhi, uint64_t blo) {
-    return ahi < bhi || (ahi == bhi && alo < blo);
-}
-// a <= b afterwards
-__device__ __forceinline__ void prek_cx(PreKey& a, PreKey& b) {
-    const bool sw = prek_less(b.hi, b.lo, a.hi, a.lo);
-    const PreKey lo = {sw ? b.hi : a.hi, sw ? b.lo : a.lo}, hi = {sw ? a.hi : b.hi, sw ? a.lo : b.lo};
-    a = lo;
-    b = hi;
-}
-
-// The K smallest keys a lane has been offered, ascending; PRE_NOKEY fills the rest.  Every index is
-// a constant after unrolling: the list lives in registers.
-template <int K>
-struct PreTop {
-    static_assert(K == 1 || K == 2 || K == 4 || K == 8, "a power of two up to FIT_KMAX");
-    PreKey k[K];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < K; ++i) k[i] = {PRE_NOKEY, PRE_NOKEY};
-    }
-    // pre_row's sink.  Wave-uniform gate: the chain runs only when some lane's key enters its list.
-    __device__ __forceinline__ void offer(bool has, uint64_t hi, uint64_t lo) {
-        const bool in = has && prek_less(hi, lo, k[K - 1].hi, k[K - 1].lo);
-        if (__ballot(in) == 0ull) return;
-        PreKey x = {in ? hi : PRE_NOKEY, in ? lo : PRE_NOKEY};
-#pragma unroll
-        for (int i = 0; i < K; ++i) prek_cx(k[i], x);  // x carries the larger one down; the last falls out
-    }
-    // The K smallest of this list and the sorted list b: min(k[i], b[K - 1 - i]) holds them as a
-    // bitonic sequence, log2(K) half-cleaner stages sort it.
-    __device__ __forceinline__ void merge(const PreKey (&b)[K]) {
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const bool lt = prek_less(b[K - 1 - i].hi, b[K - 1 - i].lo, k[i].hi, k[i].lo);
-            k[i].hi = lt ? b[K - 1 - i].hi : k[i].hi;
-            k[i].lo = lt ? b[K - 1 - i].lo : k[i].lo;
-        }
-#pragma unroll
-        for (int d = K / 2; d >= 1; d /= 2)
-#pragma unroll
-            for (int i = 0; i < K; ++i)
-                if ((i & d) == 0) prek_cx(k[i], k[i + d]);
-    }
-};
+// EvictKRow, the keys' order and PreTop<K> are fit_pre_top.h's: fit_preempt_tl_k's walk shares them.
+// k_prek_walk's fold stays spelled out below: as a call of the header's prek_fold, which says the
+// same, the compiler allocated this kernel's registers differently.
 
 __global__ __launch_bounds__(256) void k_prek_classify(
     const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
@@ -317,6 +270,34 @@ hipError_t launch_preempt_k(hipStream_t st, const NodeRec* rec, const int32_t* v
     if (kmax <= 4) return launch_prek<4>(PREK_ARGS);
     return launch_prek<8>(PREK_ARGS);
 #undef PREK_ARGS
+}
+
+namespace {
+template <int K>
+hipError_t launch_prek_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0, int32_t nt,
+                             int ncomp, int slices, int32_t kmax, const int8_t* jcomp, const PreKey* p, EvictKRow* o,
+                             int32_t* out_node, int32_t* out_vic) {
+    hipLaunchKernelGGL(k_prek_final<K>, dim3((nt + 255) / 256), dim3(256), 0, st, jl, live, nj, t0, nt, (int32_t)ncomp,
+                       slices, kmax, jcomp, p, o, out_node, out_vic);
+    return hipGetLastError();
+}
+}  // namespace
+
+// k_prek_final<K> for the positions [t0, t0 + nt) of a `_k` walk's lists (fit_preempt_tl_k.hip's walk
+// ends in it too), K the power of two at or above kmax
+hipError_t launch_preempt_k_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
+                                  int32_t nt, int ncomp, int slices, int32_t kmax, const int8_t* jcomp,
+                                  const void* part, void* out, int32_t* out_node, int32_t* out_vic) {
+    if (nt <= 0) return hipSuccess;
+    if (ncomp < 0 || ncomp > 32 || slices < 1 || kmax < 1 || kmax > FIT_KMAX) return hipErrorInvalidValue;
+    const PreKey* p = static_cast<const PreKey*>(part);
+    EvictKRow* o = static_cast<EvictKRow*>(out);
+#define PREKF_ARGS st, jl, live, nj, t0, nt, ncomp, slices, kmax, jcomp, p, o, out_node, out_vic
+    if (kmax == 1) return launch_prek_final<1>(PREKF_ARGS);
+    if (kmax == 2) return launch_prek_final<2>(PREKF_ARGS);
+    if (kmax <= 4) return launch_prek_final<4>(PREKF_ARGS);
+    return launch_prek_final<8>(PREKF_ARGS);
+#undef PREKF_ARGS
 }
 
 }  // namespace fitgpu

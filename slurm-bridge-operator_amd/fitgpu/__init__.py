@@ -1024,6 +1024,48 @@ class Engine:
         check(lib().fit_preempt_k_ms(self._h, C.byref(ms)), "fit_preempt_k_ms")
         return ms.value
 
+    # ---- victims for a multi-node job on the timeline ------------------------
+    def preempt_tl_k(self, jobs, prio, kmax: int | None = None):
+        """Every job judged alone against the current timeline (reservations included) and the lists of
+        load_victims_tl, for a start now on max(jobs.nodes_k, 1) distinct nodes at once
+        (fit_preempt_tl_k): (rows[J] of EVICT_K_DTYPE, nodes[J, kmax], victims[J, kmax]), as
+        preempt_k's.  Changes nothing.  kmax None: the largest nodes_k of the batch (at least 1)."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = None if jobs.nodes_k is None else np.ascontiguousarray(jobs.nodes_k, np.uint16)  # None: all 1
+        prio = np.ascontiguousarray(prio, np.int32)
+        j = len(part)
+        if len(prio) != j or (k is not None and len(k) != j):
+            raise ValueError("prio and nodes_k must have one entry per job")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j and k is not None else 1
+        out = np.zeros(j, EVICT_K_DTYPE)
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        victims = np.zeros((j, max(int(kmax), 0)), np.int32)
+        check(lib().fit_preempt_tl_k(self._h, j, *[_ptr(c) for c in cols], _ptr(part),
+                                     _ptr(k) if k is not None else None, _ptr(prio), int(kmax), _ptr(out), _ptr(nodes),
+                                     _ptr(victims)), "fit_preempt_tl_k")
+        return out, nodes, victims
+
+    def preempt_tl_k_device(self, cpu, mem, gpu, wall, part, nodes_k, prio, out, out_node, out_victims, kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k may be None = all 1); writes out
+        (J rows of 10 int32, the fields of EVICT_K_DTYPE in order), out_node and out_victims (J * kmax
+        int32 each).  Returns the device time of its launches in ms (fit_preempt_tl_k_ms); 0.0 for no
+        jobs."""
+        j = int(cpu.numel())
+        check(lib().fit_preempt_tl_k_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                            _ptr(nodes_k) if nodes_k is not None else None, _ptr(prio), int(kmax),
+                                            _ptr(out), _ptr(out_node), _ptr(out_victims)), "fit_preempt_tl_k_device")
+        if j == 0:
+            return 0.0
+        return self.preempt_tl_k_ms()
+
+    def preempt_tl_k_ms(self):
+        """Device time in ms of the last successful preempt_tl_k_device (fit_preempt_tl_k_ms)."""
+        ms = C.c_double()
+        check(lib().fit_preempt_tl_k_ms(self._h, C.byref(ms)), "fit_preempt_tl_k_ms")
+        return ms.value
+
     # ---- free capacity per partition and slot (DESIGN.md §2k) --------------------------------
     def free_tl(self, parts: int):
         """The capacity profile of the current timeline (fit_free_tl): a structured array of

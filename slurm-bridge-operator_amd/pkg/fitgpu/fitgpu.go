@@ -865,6 +865,44 @@ func (e *Engine) PreemptTL(j Jobs, prio []int32) ([]Evict, error) {
 	return out, nil
 }
 
+// PreemptTLK is PreemptK on the loaded timeline (fit_preempt_tl_k): every job judged alone, for a start
+// now on Need nodes at once, against the current timeline — reservations included — and the victims
+// of LoadVictimsTL.  The rows, nodes and victims are PreemptK's, PreemptKMessage gives the rows' text.
+// It changes nothing and evicts nothing.
+func (e *Engine) PreemptTLK(j Jobs, prio []int32, kmax int) ([]EvictK, []int32, []int32, error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return nil, nil, nil, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part), len(prio)) ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, nil, nil, errLen
+	}
+	if cnt == 0 {
+		return nil, nil, nil, nil
+	}
+	var nk *C.uint16_t // NULL: every job takes one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	rows := make([]C.fit_evict_k, cnt)
+	nodes, victims := make([]int32, cnt*kmax), make([]int32, cnt*kmax)
+	rc := C.fit_preempt_tl_k(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])), nk,
+		(*C.int32_t)(unsafe.Pointer(&prio[0])), C.int32_t(kmax), &rows[0],
+		(*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&victims[0])))
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	out := make([]EvictK, cnt)
+	for i := range rows {
+		out[i] = goEvictK(&rows[i])
+	}
+	return out, nodes, victims, nil
+}
+
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
 // nodes that are open there (DESIGN.md §2k).
 type Free struct {
