@@ -870,6 +870,44 @@ int fit_preempt_tl_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const i
  * fit_preempt_tl_k_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
 int fit_preempt_tl_k_ms(fit_ctx* ctx, double* ms);
 
+/* ---- report evicted victims: off the lists, onto the timeline ----------------
+ * The engine evicts nothing; a caller that HAS evicted (deleted the pods) says so here, and the
+ * loaded timeline, the lists and the shift stay loaded: ask (fit_preempt_tl_k), delete the pods,
+ * report (fit_evicted_tl), place (fit_place_tl_k starts the job at slot 0 on the freed nodes).
+ * Row i says that entry pos[i] of node[i]'s list is gone: node[i] is the caller's node id, pos[i]
+ * the position in that node's CURRENT list, 0 being the entry fit_preempt_tl would evict first.
+ * Every position of a call refers to the lists as they are before the call; rows come in any order
+ * and several may name one node.  With e' = max(end - shift, 0), the end the queries read, each
+ * row's entry (prio, end, cpu, mem, gpu)
+ *   - adds its amounts to the slots [0, e') of its node with fit_unplace_tl's arithmetic, column by
+ *     column: a -1 stays -1, any other value rises and saturates at INT32_MAX (e' = 0: nothing);
+ *   - leaves its list; the node's other entries keep their order.  The shift is unchanged.
+ * Afterwards the context answers every call exactly as one that had received fit_unplace_tl of one
+ * row per evicted entry with e' > 0 (its amounts, wall e' * slot_min, nodes_k 1, its node, start 0)
+ * and then fit_load_victims_tl of the remaining entries with every end written as e'.
+ * A node in no partition has no list (its loaded entries were validated and never used): both calls
+ * below read it as empty, so a row that names it is a position out of range.
+ * Host pointers.  FIT_E_INVAL: NULL ctx; m < 0; NULL node or pos with m > 0; a node id outside
+ * [0, n); a position outside [0, current length of that node's list); the same (node, pos) pair
+ * twice in one call.  The call then fails as a whole: everything is judged before anything is
+ * written, the timeline and the lists read back byte-identical.  FIT_E_STATE: as fit_preempt_tl.
+ * m == 0 returns 0 once the state has been judged.  A HIP error in the write phase drops the
+ * timeline and the lists (fit_load_timeline, fit_load_victims_tl).  Bounded launches, no persistent
+ * grid: neither the per-GPU persistent-launch lock nor the watchdog. */
+int fit_evicted_tl(fit_ctx* ctx, int32_t m, const int32_t* node /* m */, const int32_t* pos /* m */);
+/* Same with device pointers; the rows are judged by a kernel. */
+int fit_evicted_tl_device(fit_ctx* ctx, int32_t m, const int32_t* node, const int32_t* pos);
+/* Device time (HIP events) of the last successful fit_evicted_tl / fit_evicted_tl_device with m > 0,
+ * as fit_unplace_tl_ms; FIT_E_STATE before the first. */
+int fit_evicted_tl_ms(fit_ctx* ctx, double* ms);
+/* The current lists as a CSR by the caller's node id: what a caller mirrors.  Reading changes
+ * nothing.  off (n + 1 entries) is always written; the five columns only when all are non-NULL and
+ * cap >= off[n], ends as e' and entries in list order — a first call with cap 0 and NULL columns
+ * sizes the second.  Loading the result into a context with the same timeline gives the same answers
+ * from every query.  FIT_E_INVAL: NULL ctx or off.  FIT_E_STATE: as fit_evicted_tl. */
+int fit_read_victims_tl(fit_ctx* ctx, int32_t* off /* n + 1 */, int64_t cap, int32_t* prio, int32_t* end,
+                        int32_t* cpu, int32_t* mem, int32_t* gpu);
+
 /* ---- free capacity of every partition at every timeline slot ---------------
  * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
  * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced

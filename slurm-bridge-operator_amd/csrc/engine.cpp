@@ -367,14 +367,21 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> pk_node, pk_vic;
     HBuf<int32_t> h_pk_pick;
     // fit_load_victims_tl / fit_preempt_tl: the victims of the loaded timeline
-    // in position order, their own buffers and flag (vtl_off: nn + 1 offsets; vtl_ent: priority, end
-    // slot, raw amounts), the slots fit_advance_tl has moved the timeline by since they were loaded,
-    // and the query's rows.  The staged CSR (vs_*, vic_bad), the staged priorities and the key scratch
-    // are fit_load_victims' and fit_preempt's: every call ends synchronised on the one stream.
-    DBuf<int32_t> vs_end, vtl_off;
+    // in position order, their own buffers and flag (vtl_span: a (begin, length) pair per position;
+    // vtl_ent: vtl_total entries of priority, end slot, raw amounts — fit_evicted_tl shortens a list in
+    // place, so a span may cover less than it was loaded with), the slots fit_advance_tl has moved the
+    // timeline by since they were loaded, and the query's rows.  The staged CSR (vs_*, vic_bad), the
+    // staged priorities and the key scratch are fit_load_victims' and fit_preempt's: every call ends
+    // synchronised on the one stream.
+    DBuf<int32_t> vs_end;
+    DBuf<VicSpan> vtl_span;
     DBuf<VicTl> vtl_ent;
     bool have_vtl = false;
-    int32_t vtl_shift = 0;
+    int32_t vtl_shift = 0, vtl_total = 0;
+    // fit_evicted_tl: the staged rows of the host entry point and the *_ms
+    // diagnostic; node id -> position, the counts, the touched list and the counter words are tlr_*'s
+    DBuf<int32_t> etl_node, etl_pos;
+    double etl_ms = -1;
     QueryBufs<fit_evict> pt;
     // fit_preempt_tl_k: its rows.  The victims and the shift are fit_preempt_tl's,
     // the staged priorities, the key scratch and the picks' buffers fit_preempt_k's.
@@ -1582,7 +1589,7 @@ int preempt_tl_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* prio
                                            out, c->jcomp.p, bad);
         },
         [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
-            return launch_preempt_tl(c->st, c->tlhdr.p, c->slab.p, c->vtl_off.p, c->vtl_ent.p, ec, c->tl_slots,
+            return launch_preempt_tl(c->st, c->tlhdr.p, c->slab.p, c->vtl_span.p, c->vtl_ent.p, ec, c->tl_slots,
                                      c->tl_slot_min, c->vtl_shift, d.cpu, d.mem, d.gpu, d.wall, d.part, prio, J,
                                      c->jcomp.p, jl, live, S, c->pe_part.p, out);
         });
@@ -1602,7 +1609,7 @@ int preempt_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* pr
                                              d.nk, kmax, J, out, out_node, out_vic, c->jcomp.p, bad);
         },
         [&](const ExplainComps& ec, const int32_t* jl, const int32_t* live) {
-            return launch_preempt_tl_k(c->st, c->tlhdr.p, c->slab.p, c->vtl_off.p, c->vtl_ent.p, ec, c->tl_slots,
+            return launch_preempt_tl_k(c->st, c->tlhdr.p, c->slab.p, c->vtl_span.p, c->vtl_ent.p, ec, c->tl_slots,
                                        c->tl_slot_min, c->vtl_shift, d.cpu, d.mem, d.gpu, d.wall, d.part, prio, kmax,
                                        J, c->jcomp.p, jl, live, S, c->pe_part.p, out, out_node, out_vic);
         });
@@ -1613,19 +1620,21 @@ int preempt_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, const int32_t* pr
 // entries from the device CSR.  The lists loaded before are replaced from the first write on.
 int load_victims_tl_impl(fit_ctx* c, const int32_t* h_off, const int32_t* off, const int32_t* prio, const int32_t* end,
                          const int32_t* cpu, const int32_t* mem, const int32_t* gpu) {
-    std::vector<int32_t> hv((size_t)c->nn + 1, 0);
-    if (h_off)
-        for (int32_t i = 0; i < c->nn; ++i) {
-            const int32_t x = c->h_perm[i];
-            hv[i + 1] = hv[i] + (h_off[x + 1] - h_off[x]);
-        }
+    std::vector<VicSpan> hv((size_t)std::max(c->nn, 1), VicSpan{0, 0});
+    int32_t total = 0;
+    for (int32_t i = 0; i < c->nn; ++i) {
+        const int32_t x = c->h_perm[i];
+        hv[i] = {total, h_off ? h_off[x + 1] - h_off[x] : 0};
+        total += hv[i].len;
+    }
     c->have_vtl = false;
-    if (c->vtl_off.ensure(hv.size()) || c->vtl_ent.ensure(std::max<int32_t>(hv[c->nn], 1))) return FIT_E_OOM;
-    HIP_TRY(hipMemcpyAsync(c->vtl_off.p, hv.data(), sizeof(int32_t) * hv.size(), hipMemcpyHostToDevice, c->st));
-    if (hv[c->nn] > 0)
-        HIP_TRY(launch_vtl_build(c->st, off, prio, end, cpu, mem, gpu, c->perm.p, c->nn, c->vtl_off.p, c->vtl_ent.p));
+    if (c->vtl_span.ensure(hv.size()) || c->vtl_ent.ensure(std::max<int32_t>(total, 1))) return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->vtl_span.p, hv.data(), sizeof(VicSpan) * hv.size(), hipMemcpyHostToDevice, c->st));
+    if (total > 0)
+        HIP_TRY(launch_vtl_build(c->st, off, prio, end, cpu, mem, gpu, c->perm.p, c->nn, c->vtl_span.p, c->vtl_ent.p));
     HIP_TRY(hipStreamSynchronize(c->st));
     c->vtl_shift = 0;
+    c->vtl_total = total;
     c->have_vtl = true;
     return 0;
 }
@@ -1904,6 +1913,51 @@ int advance_tl_impl(fit_ctx* c, int32_t a, const int32_t* tc, const int32_t* tm,
     c->atl_ms = ms;
     // fit_preempt_tl reads every victim's end as max(end - shift, 0): no rewrite of the entries
     c->vtl_shift = std::min(c->vtl_shift + std::min(a, c->tl_slots), c->tl_slots);
+    return 0;
+}
+
+// --------------------------------------------------------------------------- fit_evicted_tl
+// node id -> position, then per chunk of UTL_CHUNK rows the check that marks
+// the rows' entries — every chunk before the flag is read, so all positions refer to the lists as
+// they were; a refused call takes its marks back and has written nothing else.  Then ONE apply launch,
+// a wave per touched node.  Device pointers, m > 0.
+int evicted_tl_impl(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* pos) {
+    hipStream_t st = c->st;
+    int32_t chunk = UTL_CHUNK;  // FIT_UTL_CHUNK: tests put the launch seam inside a small batch
+    if (const char* e = getenv("FIT_UTL_CHUNK")) chunk = std::max(1, std::min(atoi(e), UTL_CHUNK));
+    const int32_t cap = std::min(m, c->nn);  // distinct nodes the rows can touch
+    if (tl_rows_ensure(c, 0) || c->tlr_touched.ensure(std::max(cap, 1))) return FIT_E_OOM;
+    double ms = 0;
+    const int rc = tl_write_impl(
+        c, "fit_evicted_tl", tl_rows_flags(c, 0),
+        [&] {
+            hipError_t e = hipMemsetAsync(c->tlr_g.p, 0, sizeof(int32_t) * 4, st);
+            if (e == hipSuccess) e = hipMemsetAsync(c->tlr_cnt.p, 0, sizeof(int32_t) * (size_t)std::max(c->nn, 1), st);
+            if (e == hipSuccess) e = launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->tlr_inv.p);
+            for (int32_t t0 = 0; t0 < m && e == hipSuccess; t0 += std::min(chunk, m - t0))
+                e = launch_etl_check(st, node, pos, t0, std::min(chunk, m - t0), c->n, c->tlr_inv.p, c->vtl_span.p,
+                                     c->vtl_ent.p, c->tlr_cnt.p, c->tlr_touched.p, cap, c->tlr_g.p);
+            return e;
+        },
+        [&]() -> int {
+            if (!c->h_tlr_g.p[2]) return 0;
+            for (int32_t t0 = 0; t0 < m; t0 += std::min(chunk, m - t0))  // the marks are scratch
+                HIP_TRY(launch_etl_clear(st, node + t0, pos + t0, std::min(chunk, m - t0), c->n, c->tlr_inv.p,
+                                         c->vtl_span.p, c->vtl_ent.p));
+            HIP_TRY(hipStreamSynchronize(st));
+            return fail(FIT_E_INVAL, "a row names a node id outside [0, %d), a position outside its node's current "
+                                     "list (a node in no partition has none) or the same (node, position) twice", c->n);
+        },
+        {},
+        [&](int&) {
+            return launch_etl_apply(st, c->tlhdr.p, c->slab.p, c->tl_slots, c->vtl_shift, c->tlr_touched.p, cap,
+                                    c->vtl_span.p, c->vtl_ent.p, c->tlr_g.p);
+        },
+        &ms);
+    // a HIP error may have left marks or half-compacted lists: the lists go (fit_load_victims_tl)
+    if (rc == FIT_E_HIP) c->have_vtl = false;
+    if (rc) return rc;
+    c->etl_ms = ms;
     return 0;
 }
 
@@ -3043,6 +3097,65 @@ int fit_unplace_tl_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32
 }
 
 int fit_unplace_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::utl_ms, "fit_unplace_tl", ms); }
+
+// fit_evicted_tl / fit_evicted_tl_device, fit_read_victims_tl: fit_preempt_tl's state tests
+static int check_evicted_tl_args(fit_ctx* c, int32_t m, std::initializer_list<const void*> arrays, const char* name) {
+    const int rc = check_job_args(c, m, arrays, name, 1);
+    if (rc) return rc;
+    if (!c->have_vtl) return fail(FIT_E_STATE, "fit_load_victims_tl not called");
+    return 0;
+}
+
+int fit_evicted_tl(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* pos) {
+    const int rc = check_evicted_tl_args(c, m, {node, pos}, "fit_evicted_tl");
+    if (rc || m == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->etl_node.ensure(m) || c->etl_pos.ensure(m)) return FIT_E_OOM;
+    HIP_TRY(hipMemcpyAsync(c->etl_node.p, node, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(hipMemcpyAsync(c->etl_pos.p, pos, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, c->st));
+    return evicted_tl_impl(c, m, c->etl_node.p, c->etl_pos.p);
+}
+
+int fit_evicted_tl_device(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* pos) {
+    const int rc = check_evicted_tl_args(c, m, {node, pos}, "fit_evicted_tl");
+    if (rc || m == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return evicted_tl_impl(c, m, node, pos);
+}
+
+int fit_evicted_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::etl_ms, "fit_evicted_tl", ms); }
+
+// The current lists by the caller's node id: the spans and the entries come to the host, which puts
+// them in the caller's order (h_perm) and writes every end as the queries read it.
+int fit_read_victims_tl(fit_ctx* c, int32_t* off, int64_t cap, int32_t* prio, int32_t* end, int32_t* cpu, int32_t* mem,
+                        int32_t* gpu) {
+    const int rc = check_evicted_tl_args(c, 0, {}, "fit_read_victims_tl");
+    if (rc) return rc;
+    if (!off) return fail(FIT_E_INVAL, "null off");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<VicSpan> sp((size_t)std::max(c->nn, 1));
+    std::vector<VicTl> ent((size_t)std::max(c->vtl_total, 1));
+    HIP_TRY(hipMemcpyAsync(sp.data(), c->vtl_span.p, sizeof(VicSpan) * sp.size(), hipMemcpyDeviceToHost, c->st));
+    if (c->vtl_total > 0)
+        HIP_TRY(hipMemcpyAsync(ent.data(), c->vtl_ent.p, sizeof(VicTl) * (size_t)c->vtl_total, hipMemcpyDeviceToHost,
+                               c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    for (int32_t x = 0; x <= c->n; ++x) off[x] = 0;
+    for (int32_t i = 0; i < c->nn; ++i) off[c->h_perm[i] + 1] = sp[i].len;  // a node in no partition: empty
+    for (int32_t x = 0; x < c->n; ++x) off[x + 1] += off[x];
+    if (!prio || !end || !cpu || !mem || !gpu || cap < off[c->n]) return 0;
+    for (int32_t i = 0; i < c->nn; ++i) {
+        const VicTl* e = ent.data() + sp[i].beg;
+        for (int32_t k = 0, d = off[c->h_perm[i]]; k < sp[i].len; ++k, ++d) {
+            prio[d] = e[k].prio;
+            end[d] = std::max(e[k].end - c->vtl_shift, 0);
+            cpu[d] = e[k].cpu;
+            mem[d] = e[k].mem;
+            gpu[d] = e[k].gpu;
+        }
+    }
+    return 0;
+}
 
 // fit_hold_tl: out_state among the arrays
 int fit_hold_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,

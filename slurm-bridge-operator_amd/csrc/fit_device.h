@@ -395,7 +395,12 @@ hipError_t launch_preempt_k(hipStream_t st, const NodeRec* rec, const int32_t* v
 // One victim of a node position, 32 B (one scalar s_load_dwordx8): its priority, the slot at which it
 // hands its resources back anyway and the raw amounts it holds
 struct alignas(32) VicTl {
-    int32_t prio, end, cpu, mem, gpu, pad[3];
+    int32_t prio, end, cpu, mem, gpu, pad[3];  // pad[0]: fit_evicted_tl's mark, 0 outside that call
+};
+// The list of a node position: entries [beg, beg + len) of the entry array (one scalar 8-byte load).
+// A pair per position, not shared offsets, so that fit_evicted_tl shrinks a list in place.
+struct alignas(8) VicSpan {
+    int32_t beg, len;
 };
 // launch_vic_check's test plus 0 <= end <= H
 hipError_t launch_vtl_check(hipStream_t st, const int32_t* off, int32_t n, int64_t nvic, const int32_t* prio,
@@ -403,12 +408,12 @@ hipError_t launch_vtl_check(hipStream_t st, const int32_t* off, int32_t n, int64
                             int32_t* bad);
 hipError_t launch_vtl_build(hipStream_t st, const int32_t* off, const int32_t* prio, const int32_t* end,
                             const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* perm, int32_t nn,
-                            const int32_t* voff, VicTl* vent);
+                            const VicSpan* vspan, VicTl* vent);
 // k_pre_final (fit_preempt.hip) for the positions [t0, t0 + nt) of a walk's partials
 hipError_t launch_preempt_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
                                 int32_t nt, int ncomp, int slices, const int8_t* jcomp, const void* part, void* out);
 // shift: the slots fit_advance_tl has moved the timeline by since the victims were loaded, in [0, H]
-hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff, const VicTl* vent,
+hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, const VicSpan* vspan, const VicTl* vent,
                              const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift, const int32_t* jcpu,
                              const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                              const int32_t* jprio, int32_t nj, const int8_t* jcomp, const int32_t* jl,
@@ -420,12 +425,26 @@ hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, 
 hipError_t launch_preempt_k_final(hipStream_t st, const int32_t* jl, const int32_t* live, int32_t nj, int32_t t0,
                                   int32_t nt, int ncomp, int slices, int32_t kmax, const int8_t* jcomp,
                                   const void* part, void* out, int32_t* out_node, int32_t* out_vic);
-hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff,
+hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab, const VicSpan* vspan,
                                const VicTl* vent, const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift,
                                const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                                const uint16_t* jpart, const int32_t* jprio, int32_t kmax, int32_t nj,
                                const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices, void* part,
                                void* out, int32_t* out_node, int32_t* out_vic);
+
+// ---- fit_evicted_tl (fit_evicted_tl.hip) -------------------------------
+// The caller's report of evicted entries: row q names entry pos[q] of node[q]'s list (caller's node
+// id).  inv, cnt, touched and the counter words g are fit_unplace_tl's (g[0] touched nodes, g[2] the
+// bad-input flag; cnt[nn] and g zero before the first check).  A check marks the entries of rows
+// [t0, t0 + nj), nj <= UTL_CHUNK; clear takes the marks of a refused call back; apply, one wave per
+// touched node, adds the marked entries' windows to the run list and compacts the victim list.
+hipError_t launch_etl_check(hipStream_t st, const int32_t* node, const int32_t* pos, int32_t t0, int32_t nj, int32_t n,
+                            const int32_t* inv, const VicSpan* vspan, VicTl* vent, int32_t* cnt, int32_t* touched,
+                            int32_t cap, int32_t* g);
+hipError_t launch_etl_clear(hipStream_t st, const int32_t* node, const int32_t* pos, int32_t nj, int32_t n,
+                            const int32_t* inv, const VicSpan* vspan, VicTl* vent);
+hipError_t launch_etl_apply(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t H, int32_t shift, const int32_t* touched,
+                            int32_t cap, VicSpan* vspan, VicTl* vent, const int32_t* g);
 
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {

@@ -3,8 +3,9 @@
 // node rows (include/fitgpu.h fit_preempt_tl).  Read-only.  gfx950.
 //
 // The victims (fit_load_victims_tl) live in row order, as fit_preempt's: position x owns the entries
-// [voff[x], voff[x + 1]) of `vent`, in eviction order.  An entry is 32 bytes — priority, end slot and
-// the three RAW amounts: which entries count depends on the slot, so there is no prefix sum to keep.
+// [vspan[x].beg, + vspan[x].len) of `vent`, in eviction order (a (begin, length) pair per position, so
+// that fit_evicted_tl shrinks a list in place without moving its neighbours).  An entry is 32 bytes —
+// priority, end slot and the three RAW amounts: which entries count depends on the slot, so there is no prefix sum to keep.
 // Evicting an entry frees its amounts on the slots [0, end - shift) of its node; `shift` is what
 // fit_advance_tl has moved the timeline by since the load, a kernel argument.
 //
@@ -70,17 +71,17 @@ __global__ __launch_bounds__(256) void k_vtl_check(const int32_t* __restrict__ o
     if (err) atomicOr(bad, 1);
 }
 
-// One thread per position: its list copied in order.  off: the caller's CSR (validated), voff: the
-// position-ordered offsets (host-built from it).
+// One thread per position: its list copied in order.  off: the caller's CSR (validated), vspan: the
+// position-ordered spans (host-built from it).
 __global__ __launch_bounds__(256) void k_vtl_build(const int32_t* __restrict__ off, const int32_t* __restrict__ prio,
                                                    const int32_t* __restrict__ end, const int32_t* __restrict__ cpu,
                                                    const int32_t* __restrict__ mem, const int32_t* __restrict__ gpu,
                                                    const int32_t* __restrict__ perm, int32_t nn,
-                                                   const int32_t* __restrict__ voff, VicTl* __restrict__ vent) {
+                                                   const VicSpan* __restrict__ vspan, VicTl* __restrict__ vent) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nn) return;
     const int x = perm[i];
-    const int a = off[x], len = off[x + 1] - a, d = voff[i];
+    const int a = off[x], len = off[x + 1] - a, d = vspan[i].beg;
     for (int k = 0; k < len; ++k) {
         VicTl e;
         e.prio = prio[a + k];
@@ -103,10 +104,10 @@ hipError_t launch_vtl_check(hipStream_t st, const int32_t* off, int32_t n, int64
 
 hipError_t launch_vtl_build(hipStream_t st, const int32_t* off, const int32_t* prio, const int32_t* end,
                             const int32_t* cpu, const int32_t* mem, const int32_t* gpu, const int32_t* perm, int32_t nn,
-                            const int32_t* voff, VicTl* vent) {
+                            const VicSpan* vspan, VicTl* vent) {
     if (nn <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_vtl_build, dim3((nn + 255) / 256), dim3(256), 0, st, off, prio, end, cpu, mem, gpu, perm, nn,
-                       voff, vent);
+                       vspan, vent);
     return hipGetLastError();
 }
 
@@ -122,7 +123,7 @@ struct PtlMin {
 // grid (job tiles of the chunk, node slices); jl / live: fit_query.h's job list.  The chunk is the
 // positions [t0, t0 + nt); part: nt * gridDim.y partials, position-major.  k_pre_walk's frame and fold.
 __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptl_walk(
-    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, const int32_t* __restrict__ voff,
+    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, const VicSpan* __restrict__ vspan,
     const VicTl* __restrict__ vent, ExplainComps C, int32_t H, int32_t slot_min, int32_t shift,
     const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t nj, int32_t t0, int32_t nt,
     const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptl_walk(
     while (w.rem) {  // wave-uniform: one pass per distinct component
         const QueryRange r = query_next<PRE_WAVES>(w, C, comp, on, wave);
         const uint32_t pb = r.mine ? pbit : 0u;
-        for (int x = r.n0; x < r.n1; ++x) ptl_node(hdr[x], x, slab, pb, j, d, H, shift, voff, vent, n, key);
+        for (int x = r.n0; x < r.n1; ++x) ptl_node(hdr[x], x, slab, pb, j, d, H, shift, vspan, vent, n, key);
     }
 
 #pragma unroll
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptl_walk(
 
 // Walk and finalise, a chunk of PRE_CHUNK positions after the other, as launch_preempt; the rows were
 // set up by launch_preempt_classify.  slices: preempt_slices; part: preempt_partials.
-hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff, const VicTl* vent,
+hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, const VicSpan* vspan, const VicTl* vent,
                              const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift, const int32_t* jcpu,
                              const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                              const int32_t* jprio, int32_t nj, const int8_t* jcomp, const int32_t* jl,
@@ -200,7 +201,7 @@ hipError_t launch_preempt_tl(hipStream_t st, const TlHdr* hdr, const Seg* slab, 
     for (int32_t t0 = 0; t0 < nj; t0 += PRE_CHUNK) {
         const int32_t nt = std::min<int32_t>(nj - t0, PRE_CHUNK);
         hipLaunchKernelGGL(k_ptl_walk, dim3((nt + PRE_JOBS - 1) / PRE_JOBS, slices), dim3(PRE_WAVES * 64), 0, st, hdr,
-                           slab, voff, vent, C, H, slot_min, shift, jl, live, nj, t0, nt, jcpu, jmem, jgpu, jwall,
+                           slab, vspan, vent, C, H, slot_min, shift, jl, live, nj, t0, nt, jcpu, jmem, jgpu, jwall,
                            jpart, jprio, jcomp, static_cast<EvictCnt*>(out), p);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

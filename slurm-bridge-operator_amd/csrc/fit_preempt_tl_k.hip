@@ -36,7 +36,7 @@ namespace fitgpu {
 // (ptl_node), list stores by t < nt and i < kmax (prek_fold).
 template <int K>
 __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptlk_walk(
-    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, const int32_t* __restrict__ voff,
+    const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, const VicSpan* __restrict__ vspan,
     const VicTl* __restrict__ vent, ExplainComps C, int32_t H, int32_t slot_min, int32_t shift,
     const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t nj, int32_t t0, int32_t nt, int32_t kmax,
     const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptlk_walk(
     while (w.rem) {  // wave-uniform: one pass per distinct component
         const QueryRange r = query_next<PRE_WAVES>(w, C, comp, on, wave);
         const uint32_t pb = r.mine ? pbit : 0u;
-        for (int x = r.n0; x < r.n1; ++x) ptl_node(hdr[x], x, slab, pb, j, d, H, shift, voff, vent, n, top);
+        for (int x = r.n0; x < r.n1; ++x) ptl_node(hdr[x], x, slab, pb, j, d, H, shift, vspan, vent, n, top);
     }
 
     // the counters, the waves' lists and this slice's list of kmax keys (fit_pre_top.h)
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(PRE_WAVES * 64) void k_ptlk_walk(
 
 namespace {
 template <int K>
-hipError_t launch_ptlk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff, const VicTl* vent,
+hipError_t launch_ptlk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const VicSpan* vspan, const VicTl* vent,
                        const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift, const int32_t* jcpu,
                        const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jpart,
                        const int32_t* jprio, int32_t kmax, int32_t nj, const int8_t* jcomp, const int32_t* jl,
@@ -87,7 +87,7 @@ hipError_t launch_ptlk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const 
     for (int32_t t0 = 0; t0 < nj; t0 += PRE_CHUNK) {
         const int32_t nt = std::min<int32_t>(nj - t0, PRE_CHUNK);
         hipLaunchKernelGGL(k_ptlk_walk<K>, dim3((nt + PRE_JOBS - 1) / PRE_JOBS, slices), dim3(PRE_WAVES * 64), 0, st,
-                           hdr, slab, voff, vent, C, H, slot_min, shift, jl, live, nj, t0, nt, kmax, jcpu, jmem, jgpu,
+                           hdr, slab, vspan, vent, C, H, slot_min, shift, jl, live, nj, t0, nt, kmax, jcpu, jmem, jgpu,
                            jwall, jpart, jprio, jcomp, static_cast<EvictKRow*>(out), static_cast<PreKey*>(part));
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -100,7 +100,7 @@ hipError_t launch_ptlk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const 
 
 // Walk and finalise, a chunk of PRE_CHUNK positions after the other, as launch_preempt_k; the rows and
 // the picks were set up by launch_preempt_k_classify.  slices: preempt_slices; part: preempt_k_partials.
-hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab, const int32_t* voff,
+hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab, const VicSpan* vspan,
                                const VicTl* vent, const ExplainComps& C, int32_t H, int32_t slot_min, int32_t shift,
                                const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                                const uint16_t* jpart, const int32_t* jprio, int32_t kmax, int32_t nj,
@@ -111,7 +111,7 @@ hipError_t launch_preempt_tl_k(hipStream_t st, const TlHdr* hdr, const Seg* slab
         return hipErrorInvalidValue;
     if (H < 1 || H > TL_MAX_SLOTS || slot_min < 1 || shift < 0) return hipErrorInvalidValue;
 #define PTLK_ARGS                                                                                                  \
-    st, hdr, slab, voff, vent, C, H, slot_min, shift, jcpu, jmem, jgpu, jwall, jpart, jprio, kmax, nj, jcomp, jl, \
+    st, hdr, slab, vspan, vent, C, H, slot_min, shift, jcpu, jmem, jgpu, jwall, jpart, jprio, kmax, nj, jcomp, jl, \
         live, slices, part, out, out_node, out_vic
     if (kmax == 1) return launch_ptlk<1>(PTLK_ARGS);
     if (kmax == 2) return launch_ptlk<2>(PTLK_ARGS);

@@ -46,12 +46,13 @@ __device__ __forceinline__ void ptl_runs(const TlHdr& h, const Seg* sg, int cn, 
 template <class Sink>
 __device__ __forceinline__ void ptl_node(const TlHdr& h, int x, const Seg* __restrict__ slab, uint32_t pbit,
                                          const PreJob& j, int32_t d, int32_t H, int32_t shift,
-                                         const int32_t* __restrict__ voff, const VicTl* __restrict__ vent,
+                                         const VicSpan* __restrict__ vspan, const VicTl* __restrict__ vent,
                                          int32_t (&n)[PRE_NCNT], Sink& key) {
     const bool mb = (h.mask & pbit) != 0u;
     n[0] += mb;
-    // the list's offsets ahead of every branch: their scalar loads go out with the header's
-    const int va = voff[x], len = voff[x + 1] - va;
+    // the list's span ahead of every branch: its one 8-byte scalar load goes out with the header's
+    const VicSpan sp = vspan[x];
+    const int va = sp.beg, len = sp.len;
     const int cn = min(h.cnt, TL_MAX_SLOTS);
     const bool act = mb && d <= H && cn > 0;
     if (__ballot(act) == 0ull) return;  // wave-uniform

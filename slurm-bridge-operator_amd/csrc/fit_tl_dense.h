@@ -23,6 +23,12 @@ namespace fitgpu {
 
 constexpr int32_t TL_OVER = INT32_MIN;  // ROOM columns: the room of a slot that cannot be used at all
 
+// §2h, one column of one slot: -1 stays -1, any other value rises and saturates (fit_unplace_tl's
+// and fit_evicted_tl's op)
+__device__ __forceinline__ int32_t utl_add(int32_t v, int32_t dem) {
+    return v == -1 ? -1 : (int32_t)min<int64_t>((int64_t)v + dem, 0x7fffffff);
+}
+
 // Expand: 64 runs per load, then run by run the wave fills the run's slots.  ROOM: the columns hold
 // the room of each slot, a value below 0 becoming TL_OVER.  The caller's __syncthreads() follows.
 template <bool ROOM>

@@ -151,11 +151,6 @@ __global__ __launch_bounds__(256) void k_utl_scatter(
     }
 }
 
-// §2h, one column of one slot: -1 stays -1, any other value rises and saturates
-__device__ __forceinline__ int32_t utl_add(int32_t v, int32_t dem) {
-    return v == -1 ? -1 : (int32_t)min<int64_t>((int64_t)v + dem, 0x7fffffff);
-}
-
 // grid = an upper bound of the touched nodes; workgroup = one wave.  LDS: 3 columns of H words.
 __global__ __launch_bounds__(64) void k_utl_apply(TlHdr* hdr, Seg* slab, int32_t H, const int32_t* __restrict__ touched,
                                                   int32_t cap, int32_t* cnt, const int32_t* __restrict__ first,

@@ -1066,6 +1066,49 @@ class Engine:
         check(lib().fit_preempt_tl_k_ms(self._h, C.byref(ms)), "fit_preempt_tl_k_ms")
         return ms.value
 
+    # ---- report evicted victims: off the lists, onto the timeline -------------
+    def evicted_tl(self, node, pos):
+        """Report evicted entries (fit_evicted_tl): row i says that entry pos[i] of node[i]'s list
+        (caller's node id; position in the list as it is before the call) is gone.  Its amounts go back
+        to the slots [0, max(end - shift, 0)) of its node and it leaves the list; the timeline, the
+        other entries and the shift stay loaded."""
+        node = np.ascontiguousarray(node, np.int32)
+        pos = np.ascontiguousarray(pos, np.int32)
+        if node.ndim != 1 or node.shape != pos.shape:
+            raise ValueError("node and pos must be flat arrays of one length")
+        check(lib().fit_evicted_tl(self._h, len(node), _ptr(node) if len(node) else None,
+                                   _ptr(pos) if len(pos) else None), "fit_evicted_tl")
+
+    def evicted_tl_device(self, node, pos):
+        """node and pos torch int32 tensors resident on this GPU; the rows are judged by a kernel.
+        Returns the device time of its launches in ms (fit_evicted_tl_ms); 0.0 for no rows."""
+        m = int(node.numel())
+        check(lib().fit_evicted_tl_device(self._h, m, _ptr(node) if m else None, _ptr(pos) if m else None),
+              "fit_evicted_tl_device")
+        if m == 0:
+            return 0.0
+        return self.evicted_tl_ms()
+
+    def evicted_tl_ms(self):
+        """Device time in ms of the last successful evicted_tl / evicted_tl_device with rows (HIP events
+        on the context's stream, fit_evicted_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_evicted_tl_ms(self._h, C.byref(ms)), "fit_evicted_tl_ms")
+        return ms.value
+
+    def read_victims_tl(self):
+        """The current lists of load_victims_tl by the caller's node id (fit_read_victims_tl): a
+        synth.VictimsTL with every end as the queries read it, max(end - shift, 0); the list of a node
+        in no partition is empty.  Changes nothing."""
+        from .synth import VictimsTL
+        off = np.zeros(self.n + 1, np.int32)
+        check(lib().fit_read_victims_tl(self._h, _ptr(off), 0, None, None, None, None, None), "fit_read_victims_tl")
+        nv = int(off[-1])
+        cols = [np.zeros(nv, np.int32) for _ in range(5)]
+        if nv:
+            check(lib().fit_read_victims_tl(self._h, _ptr(off), nv, *[_ptr(c) for c in cols]), "fit_read_victims_tl")
+        return VictimsTL(off, *cols)
+
     # ---- free capacity per partition and slot (DESIGN.md §2k) --------------------------------
     def free_tl(self, parts: int):
         """The capacity profile of the current timeline (fit_free_tl): a structured array of

@@ -54,6 +54,7 @@ EXPORTS = [
     "fit_preempt_k", "fit_preempt_k_device", "fit_preempt_k_ms", "fit_preempt_k_message",
     "fit_load_victims_tl", "fit_load_victims_tl_device", "fit_preempt_tl", "fit_preempt_tl_device",
     "fit_preempt_tl_ms", "fit_preempt_tl_k", "fit_preempt_tl_k_device", "fit_preempt_tl_k_ms",
+    "fit_evicted_tl", "fit_evicted_tl_device", "fit_evicted_tl_ms", "fit_read_victims_tl",
 ]
 
 
@@ -252,6 +253,10 @@ def lib() -> C.CDLL:
         for name in ("fit_preempt_tl_k", "fit_preempt_tl_k_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P, i32, P, P, P]
         L.fit_preempt_tl_k_ms.argtypes = [P, C.POINTER(C.c_double)]
+        for name in ("fit_evicted_tl", "fit_evicted_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P, P]
+        L.fit_evicted_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_read_victims_tl.argtypes = [P, P, i64, P, P, P, P, P]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

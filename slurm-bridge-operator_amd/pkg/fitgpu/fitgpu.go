@@ -80,6 +80,7 @@ func check(rc C.int) error {
 type Engine struct {
 	ctx   *C.fit_ctx
 	slots int // horizon of the last successful LoadTimeline (FreeTL sizes its rows by it)
+	nodes int // rows of the last successful LoadNodes (ReadVictimsTL sizes Off by it)
 }
 
 func New(device int) (*Engine, error) {
@@ -125,7 +126,11 @@ func (e *Engine) LoadNodes(n Nodes) error {
 		return errLen
 	}
 	if cnt == 0 {
-		return check(C.fit_load_nodes(e.ctx, 0, nil, nil, nil, nil, nil))
+		err := check(C.fit_load_nodes(e.ctx, 0, nil, nil, nil, nil, nil))
+		if err == nil {
+			e.nodes = 0
+		}
+		return err
 	}
 	// slices of plain integers: no Go pointers inside, the library copies and does not retain
 	rc := C.fit_load_nodes(e.ctx, C.int32_t(cnt),
@@ -133,7 +138,11 @@ func (e *Engine) LoadNodes(n Nodes) error {
 		(*C.int32_t)(unsafe.Pointer(&n.GPUFree[0])), (*C.int32_t)(unsafe.Pointer(&n.AvailMin[0])),
 		(*C.uint32_t)(unsafe.Pointer(&n.PartMask[0])))
 	runtime.KeepAlive(e) // the finalizer must not destroy the context during the call
-	return check(rc)
+	err := check(rc)
+	if err == nil {
+		e.nodes = cnt
+	}
+	return err
 }
 
 // LoadPartitions takes parseResources' limits (pkg/slurm-agent/parse.go:111-190), -1 = UNLIMITED.
@@ -901,6 +910,57 @@ func (e *Engine) PreemptTLK(j Jobs, prio []int32, kmax int) ([]EvictK, []int32, 
 		out[i] = goEvictK(&rows[i])
 	}
 	return out, nodes, victims, nil
+}
+
+// EvictedTL reports evicted victims (fit_evicted_tl, DESIGN.md §2p): row i says that entry pos[i] of
+// node[i]'s list — the caller's node id, the position in the list as it is before the call, 0 being
+// the entry PreemptTL would evict first — is gone.  Its amounts go back to the slots [0, End) of its
+// node, End as the queries read it, and the entry leaves the list; the timeline, the other entries and
+// what AdvanceTL has moved them by stay loaded.  A victim that ran on several nodes is reported with
+// one row per node, each position looked up in the caller's mirror of that node's list
+// (ReadVictimsTL).  The engine evicts nothing: call it after the pods are deleted, then place the job
+// with PlaceTLK.  A bad row — an unknown node, a position outside the list, a pair named twice —
+// fails the whole call and changes nothing.
+func (e *Engine) EvictedTL(node, pos []int32) error {
+	if len(node) != len(pos) {
+		return errLen
+	}
+	if len(node) == 0 {
+		err := check(C.fit_evicted_tl(e.ctx, 0, nil, nil))
+		runtime.KeepAlive(e)
+		return err
+	}
+	rc := C.fit_evicted_tl(e.ctx, C.int32_t(len(node)), (*C.int32_t)(unsafe.Pointer(&node[0])),
+		(*C.int32_t)(unsafe.Pointer(&pos[0])))
+	runtime.KeepAlive(e)
+	return check(rc)
+}
+
+// ReadVictimsTL returns the current lists by node id (fit_read_victims_tl): what LoadVictimsTL loaded,
+// minus what EvictedTL has reported, every End as the queries read it now.  The list of a node in no
+// partition is empty.  It changes nothing.
+func (e *Engine) ReadVictimsTL() (VictimsTL, error) {
+	v := VictimsTL{Off: make([]int32, e.nodes+1)}
+	off := (*C.int32_t)(unsafe.Pointer(&v.Off[0]))
+	rc := C.fit_read_victims_tl(e.ctx, off, 0, nil, nil, nil, nil, nil) // the offsets size the columns
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return VictimsTL{}, err
+	}
+	nv := int(v.Off[e.nodes])
+	v.Prio, v.End, v.CPU = make([]int32, nv), make([]int32, nv), make([]int32, nv)
+	v.MemMiB, v.GPU = make([]int32, nv), make([]int32, nv)
+	if nv == 0 {
+		return v, nil
+	}
+	rc = C.fit_read_victims_tl(e.ctx, off, C.int64_t(nv), (*C.int32_t)(unsafe.Pointer(&v.Prio[0])),
+		(*C.int32_t)(unsafe.Pointer(&v.End[0])), (*C.int32_t)(unsafe.Pointer(&v.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&v.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&v.GPU[0])))
+	runtime.KeepAlive(e)
+	if err := check(rc); err != nil {
+		return VictimsTL{}, err
+	}
+	return v, nil
 }
 
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
