@@ -908,6 +908,49 @@ int fit_evicted_tl_ms(fit_ctx* ctx, double* ms);
 int fit_read_victims_tl(fit_ctx* ctx, int32_t* off /* n + 1 */, int64_t cap, int32_t* prio, int32_t* end,
                         int32_t* cpu, int32_t* mem, int32_t* gpu);
 
+/* ---- a node changes outside the plan: overwrite windows of the timeline -------
+ * A node goes DOWN or DRAIN, comes back, gets a maintenance window, has its avail_min shortened or
+ * lengthened or is reconfigured with other totals: the loaded timeline, the victims' lists and their
+ * shift stay loaded, and the caller writes the node's new levels here.  Let T be the dense timeline
+ * fit_read_timeline returns and H the loaded horizon.  A row with from[q] < 0 is SKIPPED whatever else
+ * it holds.  A live row covers the slots [from[q], min(to[q], H)) of node[q] (the caller's node id;
+ * to = INT32_MAX: to the horizon) and gives each column its level cpu[q], mem[q], gpu[q] >= -1,
+ * independently: -1 closes the column, a row may close one column only.  The result is that of the
+ * live rows applied one after another in index order:
+ *   T'[n][t][c] = the level of the live row with the LARGEST index that covers (n, t); T[n][t][c]
+ *   where none does.
+ * So one call equals any split of its rows into consecutive calls, a call repeated gives what one
+ * gives, and rows on different nodes or disjoint windows commute.  A resumed node is a base row
+ * [0, H) followed by the rows of its pending releases — the runs of its target timeline.
+ * A node that was in no partition at fit_load_nodes has no run list: a live row naming it is valid,
+ * writes nothing (the node reads -1 as before) and counts in *ignored; *applied counts the live rows
+ * whose node has a list.  Load a node that may come back with its partition bits and avail_min 0.
+ * Run lists stay canonical, cnt, head[] and the three ceilings of every touched node are exact
+ * afterwards, so every query and placement answers as on a timeline loaded dense-equal.  The node
+ * table (fit_read_nodes), H, slot_min, the partitions and the fit_load_victims_tl lists with their
+ * shift are untouched.  With the other writers: a column closed through slot H - 1 stays closed
+ * under every fit_advance_tl (§2i) until a row reopens slot H - 1; fit_unplace_tl and fit_evicted_tl
+ * add nothing to a closed slot, so reopen first, then hand back; fit_hold_tl refuses a row over a
+ * closed slot.
+ * Host pointers; applied and ignored may be NULL and are written on success only.  FIT_E_INVAL:
+ * NULL ctx; m < 0; a NULL array with m > 0; in a live row a node id outside [0, n), from >= H,
+ * to <= from or a level below -1.  The call then fails as a whole: the batch is judged before the
+ * first write, the timeline and every header byte stay as they were.  m == 0 returns 0 once the state
+ * has been judged, whatever the pointers are.  FIT_E_STATE: before fit_load_nodes; without a
+ * timeline; on a context with world > 1 or FIT_FLAG_COLLECTIVES.  A HIP error in the write phase
+ * drops the timeline (fit_load_timeline).  Bounded launches (four kernels per 16,384 rows), no persistent
+ * grid: neither the per-GPU persistent-launch lock nor the watchdog. */
+int fit_set_tl(fit_ctx* ctx, int32_t m, const int32_t* node /* m */, const int32_t* from /* m */,
+               const int32_t* to /* m */, const int32_t* cpu /* m */, const int32_t* mem /* m */,
+               const int32_t* gpu /* m */, int64_t* applied /* may be NULL */, int64_t* ignored /* may be NULL */);
+/* Same with the six columns as device pointers (applied and ignored stay host pointers); the rows are
+ * judged by a kernel. */
+int fit_set_tl_device(fit_ctx* ctx, int32_t m, const int32_t* node, const int32_t* from, const int32_t* to,
+                      const int32_t* cpu, const int32_t* mem, const int32_t* gpu, int64_t* applied, int64_t* ignored);
+/* Device time (HIP events) of the last successful fit_set_tl / fit_set_tl_device with a live row, as
+ * fit_unplace_tl_ms; FIT_E_STATE before the first. */
+int fit_set_tl_ms(fit_ctx* ctx, double* ms);
+
 /* ---- free capacity of every partition at every timeline slot ---------------
  * The per-partition answer while a timeline is loaded — how many GPUs partition p has free in two
  * hours, how many nodes are open at slot t, the largest one-node job that could run then — reduced

@@ -382,6 +382,10 @@ struct fit_ctx : CtxHandles {
     // diagnostic; node id -> position, the counts, the touched list and the counter words are tlr_*'s
     DBuf<int32_t> etl_node, etl_pos;
     double etl_ms = -1;
+    // fit_set_tl: the six staged columns of the host entry point, one after
+    // another, and the *_ms diagnostic; everything else is tlr_*'s, under the rule stated there
+    DBuf<int32_t> stl_rows;
+    double stl_ms = -1;
     QueryBufs<fit_evict> pt;
     // fit_preempt_tl_k: its rows.  The victims and the shift are fit_preempt_tl's,
     // the staged priorities, the key scratch and the picks' buffers fit_preempt_k's.
@@ -1961,6 +1965,62 @@ int evicted_tl_impl(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* p
     return 0;
 }
 
+// --------------------------------------------------------------------------- fit_set_tl
+// node id -> position and the check of the WHOLE batch (the flag words are the
+// counters g: the bad-input flag, the ignored rows, the windows of every chunk), then count, offsets,
+// scatter and apply per chunk of UTL_CHUNK rows.  Device pointers, m > 0; *applied and *ignored (host,
+// may be null) are written on success only.
+int set_tl_impl(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* from, const int32_t* to, const int32_t* cpu,
+                const int32_t* mem, const int32_t* gpu, int64_t* applied, int64_t* ignored) {
+    hipStream_t st = c->st;
+    int32_t chunk = UTL_CHUNK;  // FIT_UTL_CHUNK: tests put the launch seam inside a small batch
+    if (const char* e = getenv("FIT_UTL_CHUNK")) chunk = std::max(1, std::min(atoi(e), UTL_CHUNK));
+    const int64_t nchunks = ((int64_t)m + chunk - 1) / chunk;
+    const size_t wcap = (size_t)std::min(m, chunk);
+    if (tl_rows_ensure(c, nchunks) || c->tlr_touched.ensure(std::min<size_t>(wcap, std::max(c->nn, 1))) ||
+        c->tlr_win.ensure(wcap))
+        return FIT_E_OOM;
+    int64_t total = 0;
+    double ms = 0;
+    const int rc = tl_write_impl(
+        c, "fit_set_tl", tl_rows_flags(c, nchunks),
+        [&] {
+            hipError_t e = hipMemsetAsync(c->tlr_g.p, 0, sizeof(int32_t) * (4 + (size_t)nchunks), st);
+            if (e == hipSuccess) e = hipMemsetAsync(c->tlr_cnt.p, 0, sizeof(int32_t) * (size_t)std::max(c->nn, 1), st);
+            if (e == hipSuccess) e = launch_utl_inverse(st, c->tlhdr.p, c->nn, c->n, c->tlr_inv.p);
+            if (e == hipSuccess)
+                e = launch_stl_check(st, node, from, to, cpu, mem, gpu, m, c->n, c->tl_slots, chunk, c->tlr_inv.p,
+                                     c->tlr_g.p);
+            return e;
+        },
+        [&]() -> int {
+            if (c->h_tlr_g.p[2])
+                return fail(FIT_E_INVAL, "a live row has a node id outside [0, %d), from >= %d slots, to <= from or a "
+                                         "level below -1", c->n, c->tl_slots);
+            for (int64_t k = 0; k < nchunks; ++k) total += c->h_tlr_g.p[4 + k];
+            return total > 0 && c->nn > 0 ? 0 : kTlNoWrite;
+        },
+        {},
+        [&](int&) {
+            hipError_t e = hipSuccess;
+            for (int64_t k = 0; k < nchunks && e == hipSuccess; ++k) {
+                const int32_t t0 = (int32_t)(k * chunk);
+                e = launch_stl_chunk(st, c->tlhdr.p, c->slab.p, c->nn, c->tl_slots, node, from, to, cpu, mem, gpu, t0,
+                                     std::min<int32_t>(m - t0, chunk), c->h_tlr_g.p[4 + k], c->n, c->tlr_inv.p,
+                                     c->tlr_cnt.p, c->tlr_first.p, c->tlr_fill.p, c->tlr_touched.p, c->tlr_win.p,
+                                     c->tlr_g.p);
+            }
+            return e;
+        },
+        &ms);
+    if (rc) return rc;
+    const int64_t ign = c->h_tlr_g.p[3];
+    if (total + ign > 0) c->stl_ms = ms;  // a call with a live row
+    if (applied) *applied = total;
+    if (ignored) *ignored = ign;
+    return 0;
+}
+
 // --------------------------------------------------------------------------- fit_hold_tl
 // fit_unplace_tl's rows and check phase — nothing, out_state included, is
 // written before the flag is seen — then the windows of the whole call grouped by node, the judge
@@ -3124,6 +3184,40 @@ int fit_evicted_tl_device(fit_ctx* c, int32_t m, const int32_t* node, const int3
 }
 
 int fit_evicted_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::etl_ms, "fit_evicted_tl", ms); }
+
+// fit_set_tl / fit_set_tl_device: the state tests of fit_unplace_tl; the rows are the device's flag word
+int fit_set_tl(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* from, const int32_t* to, const int32_t* cpu,
+               const int32_t* mem, const int32_t* gpu, int64_t* applied, int64_t* ignored) {
+    const int rc = check_job_args(c, m, {node, from, to, cpu, mem, gpu}, "fit_set_tl", 1);
+    if (rc) return rc;
+    if (m == 0) {
+        if (applied) *applied = 0;
+        if (ignored) *ignored = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t w = (size_t)m, b = sizeof(int32_t) * w;
+    if (c->stl_rows.ensure(6 * w)) return FIT_E_OOM;
+    int32_t* d = c->stl_rows.p;
+    const int32_t* src[6] = {node, from, to, cpu, mem, gpu};
+    for (int i = 0; i < 6; ++i) HIP_TRY(hipMemcpyAsync(d + i * w, src[i], b, hipMemcpyHostToDevice, c->st));
+    return set_tl_impl(c, m, d, d + w, d + 2 * w, d + 3 * w, d + 4 * w, d + 5 * w, applied, ignored);
+}
+
+int fit_set_tl_device(fit_ctx* c, int32_t m, const int32_t* node, const int32_t* from, const int32_t* to,
+                      const int32_t* cpu, const int32_t* mem, const int32_t* gpu, int64_t* applied, int64_t* ignored) {
+    const int rc = check_job_args(c, m, {node, from, to, cpu, mem, gpu}, "fit_set_tl", 1);
+    if (rc) return rc;
+    if (m == 0) {
+        if (applied) *applied = 0;
+        if (ignored) *ignored = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return set_tl_impl(c, m, node, from, to, cpu, mem, gpu, applied, ignored);
+}
+
+int fit_set_tl_ms(fit_ctx* c, double* ms) { return tl_ms_get(c, &fit_ctx::stl_ms, "fit_set_tl", ms); }
 
 // The current lists by the caller's node id: the spans and the entries come to the host, which puts
 // them in the caller's order (h_perm) and writes every end as the queries read it.

@@ -262,7 +262,7 @@ hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab
 //   g[0]          touched nodes so far (k_utl_count)         } zero before every launch_utl_group
 //   g[1]          windows handed out so far (k_utl_offsets)  }
 //   g[2]          the bad-input flag (k_utl_check)
-//   g[3]          pad
+//   g[3]          pad (fit_set_tl: the live rows on a node without a run list, k_stl_check)
 //   g[4 + chunk]  windows of that chunk's live rows (k_utl_check; chunk = row / the check's `chunk`)
 constexpr int UTL_CHUNK = 16384;  // rows per launch sequence
 // One window of one node, 32 B: two 16-byte loads (fit_tl_dense.h runs them over the dense columns)
@@ -277,6 +277,11 @@ hipError_t launch_utl_inverse(hipStream_t st, const TlHdr* hdr, int32_t nn, int3
 hipError_t launch_utl_check(hipStream_t st, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
                             const uint16_t* jk, int32_t kmax, const int32_t* node, const int32_t* start, int32_t nj,
                             int32_t n, int32_t H, int32_t chunk, int32_t* g);
+// launch_utl_group's count and offsets alone (fit_set_tl scatters its own window format after them)
+hipError_t launch_utl_ranges(hipStream_t st, int32_t nn, const uint16_t* jk, int32_t kmax, const int32_t* node,
+                             const int32_t* start, int32_t t0, int32_t nj, int32_t windows, int32_t n,
+                             const int32_t* inv, int32_t* cnt, int32_t* first, int32_t* fill, int32_t* touched,
+                             int32_t* flag, int32_t* g);
 // flag: null, or nj words: a row that names a node in no partition gets flag[row] = 1
 hipError_t launch_utl_group(hipStream_t st, int32_t nn, int32_t H, int32_t slot_min, const int32_t* jcpu,
                             const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall, const uint16_t* jk,
@@ -445,6 +450,21 @@ hipError_t launch_etl_clear(hipStream_t st, const int32_t* node, const int32_t* 
                             const int32_t* inv, const VicSpan* vspan, VicTl* vent);
 hipError_t launch_etl_apply(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t H, int32_t shift, const int32_t* touched,
                             int32_t cap, VicSpan* vspan, VicTl* vent, const int32_t* g);
+
+// ---- fit_set_tl (fit_set_tl.hip) ---------------------------------------
+// Rows (node, from, to, cpu, mem, gpu) that overwrite windows of the loaded timeline; the row with
+// the largest index stands where rows overlap.  inv, cnt, first, fill, touched, win and the counter
+// words g are fit_unplace_tl's, with g[3] the live rows whose node has no run list (ignored) and
+// g[4 + chunk] the rows of that chunk whose node has one (its windows).  The check judges the WHOLE
+// batch (inv complete before it); a chunk is rows [t0, t0 + nj), nj <= UTL_CHUNK: count and offsets
+// (launch_utl_ranges), the scatter and the apply, one wave per touched node over four dense columns.
+hipError_t launch_stl_check(hipStream_t st, const int32_t* node, const int32_t* from, const int32_t* to,
+                            const int32_t* cpu, const int32_t* mem, const int32_t* gpu, int32_t m, int32_t n, int32_t H,
+                            int32_t chunk, const int32_t* inv, int32_t* g);
+hipError_t launch_stl_chunk(hipStream_t st, TlHdr* hdr, Seg* slab, int32_t nn, int32_t H, const int32_t* node,
+                            const int32_t* from, const int32_t* to, const int32_t* cpu, const int32_t* mem,
+                            const int32_t* gpu, int32_t t0, int32_t nj, int32_t windows, int32_t n, const int32_t* inv,
+                            int32_t* cnt, int32_t* first, int32_t* fill, int32_t* touched, TlWin* win, int32_t* g);
 
 // Persistent engines' watchdog trip record (fit_engine_ctl.h; read back by engine.cpp).
 enum TripSite : unsigned {

@@ -1,9 +1,11 @@
 // fit_tl_dense.h — the dense per-node edit of a run list, shared by the calls that write windows to
 // the loaded timeline: fit_unplace_tl (k_utl_apply) and fit_hold_tl (k_htl_judge, k_htl_apply); the
 // header refresh at its end is also fit_advance_tl's (k_atl_move) and fit_place_tl_k's
-// (k_ptlk_commit).  DESIGN.md §3.16.  Every piece is __forceinline__ and is called by one whole wave
-// (a 64-thread workgroup, or one wave of a larger one for tl_refresh_head), so the kernels built from
-// them compile to what they were when each spelled the pieces out.
+// (k_ptlk_commit); fit_evicted_tl (k_etl_apply) and fit_set_tl (k_stl_apply, with
+// tl_dense_windows_slots for tl_dense_windows) run the same edit with their own window step.
+// DESIGN.md §3.16.  Every piece is __forceinline__ and is called by one whole wave (a 64-thread
+// workgroup, or one wave of a larger one for tl_refresh_head), so the kernels built from them compile
+// to what they were when each spelled the pieces out.
 //
 // The edit: ONE wave per node expands the node's run list to H slots x 3 columns in LDS
 // (tl_dense_expand), runs every window of the node over the columns, 64 slots per step
@@ -90,6 +92,33 @@ __device__ __forceinline__ bool tl_dense_windows(const TlWin* __restrict__ win, 
         }
     }
     return any;
+}
+
+// tl_dense_windows' sibling for an operation that is not a function of (value, demand) per column
+// (fit_set_tl: the largest row index stands, kept in a fourth column): for each window of
+// win[w0, w0 + nw), 64 per load and each broadcast in turn, op(slot, cpu, mem, gpu, row) for every
+// slot of the window; the columns are op's own.  Slot s is lane s % 64's in EVERY window (a window
+// starts its walk at the 64-slot boundary at or below its first slot), so whatever op keeps per slot
+// is read and written by one lane in program order: the windows need no barrier between them.  The
+// caller's barriers stand between this and the passes that walk the slots otherwise.
+template <class SlotOp>
+__device__ __forceinline__ void tl_dense_windows_slots(const TlWin* __restrict__ win, int32_t w0, int32_t nw,
+                                                       int32_t wcap, int32_t H, int lane, SlotOp op) {
+    for (int i0 = 0; i0 < nw; i0 += 64) {
+        const int32_t wi = w0 + i0 + lane;
+        const bool have = i0 + lane < nw && wi >= 0 && wi < wcap;
+        const TlWin mine = have ? win[wi] : TlWin{0, 0, 0, 0, 0, 0, {0, 0}};
+        const int m = min(64, nw - i0);
+        for (int k = 0; k < m; ++k) {
+            // k is wave-uniform: scalar reads of lane k's registers, no LDS round trip per window
+            const int32_t ws = max(__builtin_amdgcn_readlane(mine.s, k), 0);
+            const int32_t we = min(__builtin_amdgcn_readlane(mine.e, k), H);
+            const int32_t jc = __builtin_amdgcn_readlane(mine.cpu, k), jm = __builtin_amdgcn_readlane(mine.mem, k);
+            const int32_t jg = __builtin_amdgcn_readlane(mine.gpu, k), row = __builtin_amdgcn_readlane(mine.row, k);
+            for (int s = (ws & ~63) + lane; s < we; s += 64)
+                if (s >= ws) op(s, jc, jm, jg, row);
+        }
+    }
 }
 
 // Write back: slot s ends a run when it is the last or its successor differs (ballot + lanes-below

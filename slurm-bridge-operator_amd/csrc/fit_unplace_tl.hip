@@ -208,17 +208,29 @@ hipError_t launch_utl_group(hipStream_t st, int32_t nn, int32_t H, int32_t slot_
                             int32_t kmax, const int32_t* node, const int32_t* start, int32_t t0, int32_t nj,
                             int32_t windows, int32_t n, const int32_t* inv, int32_t* cnt, int32_t* first,
                             int32_t* fill, int32_t* touched, TlWin* win, int32_t* flag, int32_t* g) {
-    if (kmax < 1 || kmax > FIT_KMAX || windows < 1 || (int64_t)windows > (int64_t)nj * kmax || H < 1 ||
-        H > TL_MAX_SLOTS || slot_min < 1 || t0 < 0 || nn < 0)
+    if (H < 1 || H > TL_MAX_SLOTS || slot_min < 1) return hipErrorInvalidValue;
+    const hipError_t e = launch_utl_ranges(st, nn, jk, kmax, node, start, t0, nj, windows, n, inv, cnt, first, fill,
+                                           touched, flag, g);
+    if (e != hipSuccess || std::min(windows, nn) <= 0) return e;
+    hipLaunchKernelGGL(k_utl_scatter, dim3((nj + 255) / 256), dim3(256), 0, st, jcpu, jmem, jgpu, jwall, jk, kmax, node,
+                       start, t0, nj, H, slot_min, n, inv, fill, win, windows);
+    return hipGetLastError();
+}
+
+// The first two steps of launch_utl_group, which need only a row's node list and start: the count
+// per node with the touched list, then every touched node's range of the window array.  fit_set_tl's
+// rows (one node each, `from` for start) take them as they are and scatter their own window format.
+hipError_t launch_utl_ranges(hipStream_t st, int32_t nn, const uint16_t* jk, int32_t kmax, const int32_t* node,
+                             const int32_t* start, int32_t t0, int32_t nj, int32_t windows, int32_t n,
+                             const int32_t* inv, int32_t* cnt, int32_t* first, int32_t* fill, int32_t* touched,
+                             int32_t* flag, int32_t* g) {
+    if (kmax < 1 || kmax > FIT_KMAX || windows < 1 || (int64_t)windows > (int64_t)nj * kmax || t0 < 0 || nn < 0)
         return hipErrorInvalidValue;
     const int32_t cap = std::min(windows, nn);  // distinct nodes the rows can touch
     const dim3 rows((nj + 255) / 256), th(256);
     hipLaunchKernelGGL(k_utl_count, rows, th, 0, st, jk, kmax, node, start, t0, nj, n, inv, cnt, touched, cap, flag, g);
-    if (cap > 0) {
+    if (cap > 0)
         hipLaunchKernelGGL(k_utl_offsets, dim3((cap + 255) / 256), th, 0, st, touched, cap, cnt, first, fill, g);
-        hipLaunchKernelGGL(k_utl_scatter, rows, th, 0, st, jcpu, jmem, jgpu, jwall, jk, kmax, node, start, t0, nj, H,
-                           slot_min, n, inv, fill, win, windows);
-    }
     return hipGetLastError();
 }
 

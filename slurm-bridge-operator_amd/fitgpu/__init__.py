@@ -1109,6 +1109,42 @@ class Engine:
             check(lib().fit_read_victims_tl(self._h, _ptr(off), nv, *[_ptr(c) for c in cols]), "fit_read_victims_tl")
         return VictimsTL(off, *cols)
 
+    # ---- a node changes outside the plan: overwrite windows of the timeline ----
+    def set_tl(self, node, frm, to, levels):
+        """Overwrite windows of the current timeline (fit_set_tl): row i sets the slots
+        [frm[i], min(to[i], H)) of node[i] (caller's node id) to levels[i] = (cpu, mem, gpu), each
+        >= -1, -1 closing the column; rows with frm < 0 are skipped, and where rows overlap the one with
+        the largest index stands.  levels is int32 [m, 3].  Returns (applied, ignored): the live rows
+        whose node has a run list, and those on a node that was loaded in no partition."""
+        node = np.ascontiguousarray(node, np.int32)
+        frm = np.ascontiguousarray(frm, np.int32)
+        to = np.ascontiguousarray(to, np.int32)
+        levels = np.asarray(levels, np.int32)
+        m = len(node) if node.ndim == 1 else -1
+        if m < 0 or frm.shape != (m,) or to.shape != (m,) or levels.shape != (m, 3):
+            raise ValueError("node, frm and to must be flat arrays of one length m, levels [m, 3]")
+        cols = [node, frm, to] + [np.ascontiguousarray(levels[:, i]) for i in range(3)]
+        applied, ignored = C.c_int64(), C.c_int64()
+        check(lib().fit_set_tl(self._h, m, *[_ptr(c) if m else None for c in cols], C.byref(applied),
+                               C.byref(ignored)), "fit_set_tl")
+        return applied.value, ignored.value
+
+    def set_tl_device(self, node, frm, to, cpu, mem, gpu):
+        """The six columns as torch int32 tensors resident on this GPU, m entries each; the rows are
+        judged by a kernel.  Returns (applied, ignored)."""
+        m = int(node.numel())
+        applied, ignored = C.c_int64(), C.c_int64()
+        check(lib().fit_set_tl_device(self._h, m, *[_ptr(t) if m else None for t in (node, frm, to, cpu, mem, gpu)],
+                                      C.byref(applied), C.byref(ignored)), "fit_set_tl_device")
+        return applied.value, ignored.value
+
+    def set_tl_ms(self):
+        """Device time in ms of the last successful set_tl / set_tl_device with a live row (HIP events
+        on the context's stream, fit_set_tl_ms)."""
+        ms = C.c_double()
+        check(lib().fit_set_tl_ms(self._h, C.byref(ms)), "fit_set_tl_ms")
+        return ms.value
+
     # ---- free capacity per partition and slot (DESIGN.md §2k) --------------------------------
     def free_tl(self, parts: int):
         """The capacity profile of the current timeline (fit_free_tl): a structured array of

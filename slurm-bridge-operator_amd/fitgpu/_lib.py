@@ -55,6 +55,7 @@ EXPORTS = [
     "fit_load_victims_tl", "fit_load_victims_tl_device", "fit_preempt_tl", "fit_preempt_tl_device",
     "fit_preempt_tl_ms", "fit_preempt_tl_k", "fit_preempt_tl_k_device", "fit_preempt_tl_k_ms",
     "fit_evicted_tl", "fit_evicted_tl_device", "fit_evicted_tl_ms", "fit_read_victims_tl",
+    "fit_set_tl", "fit_set_tl_device", "fit_set_tl_ms",
 ]
 
 
@@ -257,6 +258,9 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P]
         L.fit_evicted_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_victims_tl.argtypes = [P, P, i64, P, P, P, P, P]
+        for name in ("fit_set_tl", "fit_set_tl_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, C.POINTER(i64), C.POINTER(i64)]
+        L.fit_set_tl_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_read_nodes.argtypes = [P, P, P, P]
         L.fit_load_timeline.argtypes = [P, i32, i32, P, P, P, P, P]
         L.fit_load_timeline_device.argtypes = [P, i32, i32, P, i64, P, P, P, P]

@@ -963,6 +963,44 @@ func (e *Engine) ReadVictimsTL() (VictimsTL, error) {
 	return v, nil
 }
 
+// TLSet is one fit_set_tl row (DESIGN.md §2q): the slots [From, min(To, H)) of Node, the caller's node
+// id, get the levels CPU, MemMiB and GPU, each >= -1; -1 closes the column.  From < 0: the row is
+// skipped.  To = math.MaxInt32: to the horizon.
+type TLSet struct {
+	Node, From, To   int32
+	CPU, MemMiB, GPU int32
+}
+
+// SetTL overwrites windows of the loaded timeline when a node changes outside the plan (fit_set_tl):
+// it drains, resumes, gets a maintenance window, another avail_min or other totals.  Where rows
+// overlap, the one with the largest index stands, so a resumed node is a base row over the whole
+// horizon followed by the rows of its pending releases.  applied counts the live rows whose node has a
+// run list, ignored those on a node that was loaded in no partition (it keeps reading -1: load a node
+// that may come back with its partition bits and avail_min 0).  The node table, the victims' lists and
+// what AdvanceTL has moved them by stay as they are.  A bad live row — an unknown node, From at or
+// beyond the horizon, To <= From, a level below -1 — fails the whole call and changes nothing.
+func (e *Engine) SetTL(rows []TLSet) (applied, ignored int64, err error) {
+	var a, g C.int64_t
+	m := len(rows)
+	if m == 0 {
+		err = check(C.fit_set_tl(e.ctx, 0, nil, nil, nil, nil, nil, nil, &a, &g))
+		runtime.KeepAlive(e)
+		return int64(a), int64(g), err
+	}
+	cols := make([]int32, 6*m) // node, from, to, cpu, mem, gpu: one column after another
+	for i, r := range rows {
+		cols[i], cols[m+i], cols[2*m+i] = r.Node, r.From, r.To
+		cols[3*m+i], cols[4*m+i], cols[5*m+i] = r.CPU, r.MemMiB, r.GPU
+	}
+	col := func(k int) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(&cols[k*m])) }
+	rc := C.fit_set_tl(e.ctx, C.int32_t(m), col(0), col(1), col(2), col(3), col(4), col(5), &a, &g)
+	runtime.KeepAlive(e)
+	if err = check(rc); err != nil {
+		return 0, 0, err
+	}
+	return int64(a), int64(g), nil
+}
+
 // Free is one fit_free row: the free capacity of one partition at one timeline slot, over the member
 // nodes that are open there (DESIGN.md §2k).
 type Free struct {
