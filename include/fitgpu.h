@@ -397,6 +397,52 @@ int fit_when_k_ms(fit_ctx* ctx, double* ms);
  *                       the codes with the same numbers, verbatim */
 int fit_when_k_message(const fit_eta_k* e, char* buf, int32_t buflen);
 
+/* ---- begin and deadline per job: the multi-node pair with a window ------------
+ * fit_when_k and fit_place_tl_k search the whole horizon from slot 0.  The two calls below take two
+ * more optional job columns — `sbatch --begin` / `--deadline`, the planned end of a dependency's
+ * parent, the recorded start of a row fit_hold_tl refused — and are otherwise §2f / §2g word for
+ * word.  Per job, with H the timeline's slots and d = max(1, ceil(wall / slot_min)):
+ *   from  = clamp(not_before, 0, H)       until = clamp(deadline, 0, H)
+ *   A     = { s : from <= s and s + d <= until }       the allowed starts
+ * No value of either column is an error: a negative not_before is 0 (what is left of a begin time
+ * after subtracting fit_advance_tl's `a`), a deadline <= 0 has passed, a deadline >= H (INT32_MAX)
+ * is none.  S_n, cnt(s), the score, the node order and the partition rejections are fit_when_k's;
+ * `start` is the smallest s in A with cnt(s) >= need, the nodes are the need smallest (score, node
+ * id) among the members with start in S_n, the score from the minima over [start, start + d) only.
+ * The row is a fit_eta_k:
+ *   hosts   members with S_n ∩ A not empty
+ *   now     cnt(from) if from is in A, else 0: the nodes free at the job's earliest allowed start
+ *   ready   cnt(start); members, dur, need, wait_min as fit_when_k's
+ * Codes 1-5 as fit_when_k, same precedence; with a start FIT_ETA_NOW when start == 0, else
+ * FIT_ETA_LATER; without one FIT_ETA_HORIZON when A is the whole range (from == 0 and until == H),
+ * else FIT_ETA_WINDOW.  Code 8 comes from fit_when_k_win alone; fit_when_message and
+ * fit_when_k_message refuse it.  With both columns NULL, or any columns that clamp to (0, H), rows
+ * and nodes equal fit_when_k's field for field.  If fit_when_k's start lies in A, start and nodes
+ * are fit_when_k's.  Not here: dependencies INSIDE one call (a parent may sit in another partition
+ * component, whose jobs are placed concurrently: chain two calls, not_before = out_start + dur of
+ * the parent), and windows for fit_when / fit_place_tl (nodes_k <= 1 here gives their answers). */
+#define FIT_ETA_WINDOW 8 /* no s in A has cnt(s) >= need, and A is not the whole range */
+/* Host pointers; nodes_k, not_before and deadline may each be NULL (all 1 / all 0 / none).  out,
+ * out_node, j == 0, FIT_E_INVAL, FIT_E_STATE and the launches are fit_when_k's: read-only, bounded
+ * launches per chunk of 16,384 jobs, no lock, no watchdog.  A job whose A is empty walks nothing. */
+int fit_when_k_win(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                   const int32_t* not_before /* j; NULL = all 0 */, const int32_t* deadline /* j; NULL = none */,
+                   fit_eta_k* out, int32_t* out_node);
+/* Same with device pointers (inputs resident in HBM, rows and nodes written in HBM). */
+int fit_when_k_win_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                          const int32_t* not_before, const int32_t* deadline, fit_eta_k* out,
+                          int32_t* out_node);
+/* Diagnostic, for measurement only (tools/win_tl_bench.py): device time of the last successful
+ * fit_when_k_win_device on this context, in milliseconds.  FIT_E_STATE when there has been none. */
+int fit_when_k_win_ms(fit_ctx* ctx, double* ms);
+/* The row as one line of text, as fit_when_k_message (same returns, 256 bytes always suffice):
+ *   FIT_ETA_WINDOW      "no start inside its window for <need> nodes at once: <hosts>/<members>
+ *                        nodes can run it there"   — on one line
+ *   every other code    fit_when_k_message's text, verbatim */
+int fit_when_k_win_message(const fit_eta_k* e, char* buf, int32_t buflen);
+
 /* ---- priority-order backfill of multi-node jobs -----------------------------
  * fit_place_tl for jobs of nodes_k nodes, the committing half of fit_when_k: jobs 0 .. j-1 in
  * index order, each judged against the timeline AS THE JOBS BEFORE IT LEFT IT.  Partition
@@ -431,6 +477,26 @@ int fit_place_tl_k(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* m
 int fit_place_tl_k_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
                           const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
                           int32_t* out_node /* j * kmax */, int32_t* out_start /* j */, fit_stats* stats);
+/* fit_place_tl_k with fit_when_k_win's start rule: the queue runs in index order,
+ * each job judged against the timeline as the jobs before it left it, its start the smallest s in
+ * its own A with cnt(s) >= need, the reservation all-or-nothing on [start, start + d) of each node.
+ * A job without an allowed start is FIT_UNPLACED and consumes nothing, so the jobs behind it are
+ * never judged against a reservation outside its window.  Every placed job has from <= start and
+ * start + d <= until.  Job 0's result is fit_when_k_win's answer on the timeline as loaded; with
+ * both columns NULL, or any that clamp to (0, H), nodes, starts, stats and the final timeline are
+ * fit_place_tl_k's.  fit_unplace_tl of the outputs restores the timeline bit for bit, and after a
+ * reload fit_hold_tl of them holds every row.  Outputs, stats (engine = 4), j == 0, errors, state
+ * rules and launches are fit_place_tl_k's; a failed call leaves the timeline byte-identical.
+ * Host pointers; nodes_k, not_before, deadline and stats may each be NULL. */
+int fit_place_tl_k_win(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                       const int32_t* not_before /* j; NULL = all 0 */, const int32_t* deadline /* j; NULL = none */,
+                       int32_t* out_node /* j * kmax */, int32_t* out_start /* j */, fit_stats* stats);
+/* Same with device pointers (inputs resident in HBM, outputs written in HBM). */
+int fit_place_tl_k_win_device(fit_ctx* ctx, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                              const int32_t* wall, const uint16_t* part, const uint16_t* nodes_k, int32_t kmax,
+                              const int32_t* not_before, const int32_t* deadline, int32_t* out_node /* j * kmax */,
+                              int32_t* out_start /* j */, fit_stats* stats);
 
 /* ---- hand reservations back to the timeline ---------------------------------
  * The inverse of fit_place_tl / fit_place_tl_k, for a deleted pod or a running job that ends

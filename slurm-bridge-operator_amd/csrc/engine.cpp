@@ -323,6 +323,10 @@ struct fit_ctx : CtxHandles {
     DBuf<int32_t> wk_node, wk_diff;
     HBuf<int32_t> h_wk_node;
     DBuf<unsigned long long> wk_top;
+    // fit_when_k_win / fit_place_tl_k_win: the flag word, pinned copy and *_ms of the windowed query
+    // (its rows' scratch is fit_when_k's), and the host entry points' staged window columns
+    QueryBufs<fit_eta_k> wkw;
+    DBuf<int32_t> win_nb, win_dl;
     // fit_place_tl_k: the placed count of the commit launches (device, pinned)
     DBuf<int32_t> ptlk_cnt;
     HBuf<int32_t> h_ptlk;
@@ -1441,7 +1445,8 @@ int explain_impl(fit_ctx* c, int32_t J, const JobCols& d, fit_why* out, int32_t*
 // valid once the caller has drained the stream.
 static_assert(ETA_NOW == FIT_ETA_NOW && ETA_PARTITION == FIT_ETA_PARTITION && ETA_LIMIT_TIME == FIT_ETA_LIMIT_TIME &&
                   ETA_LIMIT_CPUS == FIT_ETA_LIMIT_CPUS && ETA_LIMIT_MEM == FIT_ETA_LIMIT_MEM &&
-                  ETA_NO_NODES == FIT_ETA_NO_NODES && ETA_LATER == FIT_ETA_LATER && ETA_HORIZON == FIT_ETA_HORIZON,
+                  ETA_NO_NODES == FIT_ETA_NO_NODES && ETA_LATER == FIT_ETA_LATER && ETA_HORIZON == FIT_ETA_HORIZON &&
+                      ETA_WINDOW == FIT_ETA_WINDOW,
               "fit_device.h and fitgpu.h disagree");
 static_assert(sizeof(fit_eta) == 32, "fit_eta is 32 bytes");
 // nodes a wave walks at least before the node range is sliced further (explain_slices; fit_explain
@@ -1673,8 +1678,14 @@ int whenk_slices(int32_t nj, int32_t maxn, int cus) {
     return (int)std::max<int64_t>(1, std::min<int64_t>({want, fit, (int64_t)WHENK_MAX_SLICES}));
 }
 
+// The window columns of fit_when_k_win / fit_place_tl_k_win on the device, either
+// nullptr: not_before all 0, deadline none.  No WinDev at all: the unwindowed kernels.
+struct WinDev {
+    const int32_t *nb, *dl;
+};
+
 int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k* out, int32_t* out_node,
-                int32_t* bad) {
+                int32_t* bad, const WinDev* win = nullptr) {
     hipStream_t st = c->st;
     const int C = c->ncomp, H = c->tl_slots;
     const int32_t chunk = std::min<int32_t>(J, WHENK_CHUNK);
@@ -1691,10 +1702,17 @@ int when_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, fit_eta_k
     const int32_t *jl, *live;
     if (const int rc = query_joblist(c, J, WHENK_GROUP, &jl, &live)) return rc;
     const ExplainComps ec = query_comps(c);
-    for (int32_t t0 = 0; t0 < J; t0 += WHENK_CHUNK)
-        HIP_TRY(launch_whenk_chunk(st, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, d.cpu, d.mem, d.gpu, d.wall,
-                                   d.part, t0, std::min<int32_t>(J - t0, WHENK_CHUNK), J, kmax, c->jcomp.p, jl, live, S,
-                                   c->wk_diff.p, c->wk_top.p, out, out_node));
+    for (int32_t t0 = 0; t0 < J; t0 += WHENK_CHUNK) {
+        const int32_t nj = std::min<int32_t>(J - t0, WHENK_CHUNK);
+        if (win)
+            HIP_TRY(launch_whenk_chunk_win(st, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, d.cpu, d.mem, d.gpu, d.wall,
+                                           d.part, t0, nj, J, kmax, c->jcomp.p, jl, live, S, c->wk_diff.p, c->wk_top.p,
+                                           out, out_node, win->nb, win->dl));
+        else
+            HIP_TRY(launch_whenk_chunk(st, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, d.cpu, d.mem, d.gpu, d.wall,
+                                       d.part, t0, nj, J, kmax, c->jcomp.p, jl, live, S, c->wk_diff.p, c->wk_top.p, out,
+                                       out_node));
+    }
     return 0;
 }
 
@@ -1759,7 +1777,7 @@ int tl_write_impl(fit_ctx* c, const char* name, TlBack flags, Check check, Verdi
 // offsets; then k_ptlk_commit per chunk of PTLK_CHUNK jobs of every component's list, one workgroup
 // per component.  Device pointers; out (J * kmax) and outs (J) are valid on return.
 int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32_t* out, int32_t* outs,
-                    fit_stats* stats) {
+                    fit_stats* stats, const WinDev* win = nullptr) {
     const double t0 = now_ms();
     fit_stats S;
     memset(&S, 0, sizeof S);
@@ -1779,7 +1797,7 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
     int32_t chunk = PTLK_CHUNK;  // FIT_PTLK_CHUNK: tests put the launch seam inside a small batch
     if (const char* e = getenv("FIT_PTLK_CHUNK")) chunk = std::max(1, std::min(atoi(e), PTLK_CHUNK));
     const int rc = tl_write_impl(
-        c, "fit_place_tl_k", {c->h_jls.p, g, sizeof(int32_t) * ns},
+        c, win ? "fit_place_tl_k_win" : "fit_place_tl_k", {c->h_jls.p, g, sizeof(int32_t) * ns},
         [&] {
             hipError_t e = launch_ptlk_classify(st, c->d_ptab.p, c->np, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax,
                                                 J, out, outs, c->jcomp.p);
@@ -1802,9 +1820,12 @@ int place_tl_k_impl(fit_ctx* c, int32_t J, const JobCols& d, int32_t kmax, int32
             hipError_t e = hipSuccess;
             int32_t done = 0;
             for (; done < maxlen && e == hipSuccess; done += chunk)
-                e = launch_ptlk_commit(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd, done,
-                                       chunk, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs,
-                                       c->ptlk_cnt.p);
+                e = win ? launch_ptlk_commit_win(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd,
+                                                 done, chunk, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs,
+                                                 c->ptlk_cnt.p, win->nb, win->dl)
+                        : launch_ptlk_commit(st, threads, c->tlhdr.p, c->slab.p, ec, H, c->tl_slot_min, c->jl.p, jbd, done,
+                                             chunk, d.cpu, d.mem, d.gpu, d.wall, d.part, d.nk, kmax, out, outs,
+                                             c->ptlk_cnt.p);
             if (e != hipSuccess && done <= chunk)  // the very first commit launch: nothing is reserved yet
                 kept = fail(FIT_E_HIP, "k_ptlk_commit launch failed: %s", hipGetErrorString(e));
             return e;
@@ -2516,8 +2537,9 @@ int fit_when_ms(fit_ctx* c, double* ms) {
 
 // fit_when_k / fit_when_k_device: fit_when's tests, then kmax (nodes_k against kmax is the
 // device's flag word)
-static int check_when_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax) {
-    const int rc = check_job_args(c, j, arrays, "fit_when_k", 1);
+static int check_when_k_args(fit_ctx* c, int32_t j, std::initializer_list<const void*> arrays, int32_t kmax,
+                             const char* name = "fit_when_k") {
+    const int rc = check_job_args(c, j, arrays, name, 1);
     if (rc) return rc;
     if (kmax < 1 || kmax > FIT_MAX_K) return fail(FIT_E_INVAL, "kmax=%d (1..%d)", kmax, FIT_MAX_K);
     return 0;
@@ -2565,6 +2587,62 @@ int fit_when_k_ms(fit_ctx* c, double* ms) {
     if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
     if (c->wk.ms < 0) return fail(FIT_E_STATE, "no fit_when_k_device yet");
     *ms = c->wk.ms;
+    return 0;
+}
+
+// fit_when_k_win / fit_place_tl_k_win: the optional window columns of a host entry point, one copy
+// each into the context's own columns (j > 0); a NULL column stays NULL
+static int stage_window(fit_ctx* c, int32_t j, const int32_t* not_before, const int32_t* deadline, WinDev& w) {
+    const size_t b = sizeof(int32_t) * (size_t)j;
+    if ((not_before && c->win_nb.ensure(j)) || (deadline && c->win_dl.ensure(j))) return FIT_E_OOM;
+    if (not_before) HIP_TRY(hipMemcpyAsync(c->win_nb.p, not_before, b, hipMemcpyHostToDevice, c->st));
+    if (deadline) HIP_TRY(hipMemcpyAsync(c->win_dl.p, deadline, b, hipMemcpyHostToDevice, c->st));
+    w = {not_before ? c->win_nb.p : nullptr, deadline ? c->win_dl.p : nullptr};
+    return 0;
+}
+
+int fit_when_k_win(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                   const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
+                   const int32_t* not_before, const int32_t* deadline, fit_eta_k* out, int32_t* out_node) {
+    const int rc = check_when_k_args(c, j, {cpu, mem, gpu, wall, part, out, out_node}, kmax, "fit_when_k_win");
+    if (rc || j == 0) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nn = (size_t)j * kmax;
+    if (c->wk_node.ensure(nn) || c->h_wk_node.ensure(nn)) return FIT_E_OOM;
+    WinDev w;
+    if (const int e = stage_window(c, j, not_before, deadline, w)) return e;
+    const int r = query_host(
+        c, c->wkw, j, cpu, mem, gpu, wall, part, nk, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_eta_k* rows, int32_t* bad) {
+            const int e = when_k_impl(x, n, d, kmax, rows, x->wk_node.p, bad, &w);
+            if (e) return e;
+            HIP_TRY(hipMemcpyAsync(x->h_wk_node.p, x->wk_node.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, x->st));
+            return 0;
+        },
+        bad_when_k_job);
+    if (r) return r;
+    memcpy(out_node, c->h_wk_node.p, sizeof(int32_t) * nn);
+    return 0;
+}
+
+int fit_when_k_win_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                          const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
+                          const int32_t* not_before, const int32_t* deadline, fit_eta_k* out, int32_t* out_node) {
+    const int rc = check_when_k_args(c, j, {cpu, mem, gpu, wall, part, out, out_node}, kmax, "fit_when_k_win");
+    if (rc || j == 0) return rc;
+    const WinDev w{not_before, deadline};
+    return query_device(
+        c, c->wkw, j, {cpu, mem, gpu, wall, part, nk}, out,
+        [&](fit_ctx* x, int32_t n, const JobCols& d, fit_eta_k* rows, int32_t* bad) {
+            return when_k_impl(x, n, d, kmax, rows, out_node, bad, &w);
+        },
+        bad_when_k_job);
+}
+
+int fit_when_k_win_ms(fit_ctx* c, double* ms) {
+    if (!c || !ms) return fail(FIT_E_INVAL, "null argument");
+    if (c->wkw.ms < 0) return fail(FIT_E_STATE, "no fit_when_k_win_device yet");
+    *ms = c->wkw.ms;
     return 0;
 }
 
@@ -3126,6 +3204,49 @@ int fit_place_tl_k_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32
     }
     HIP_TRY(hipSetDevice(c->device));
     return place_tl_k_impl(c, j, {cpu, mem, gpu, wall, part, nk}, kmax, out_node, out_start, stats);
+}
+
+int fit_place_tl_k_win(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                       const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
+                       const int32_t* not_before, const int32_t* deadline, int32_t* out_node, int32_t* out_start,
+                       fit_stats* stats) {
+    int rc = check_tl_rows_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax, "fit_place_tl_k_win");
+    if (rc) return rc;
+    if (j == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    JobCols d;
+    rc = stage_columns(c, j, cpu, mem, gpu, wall, part, true, nk, d);
+    if (rc) return rc;
+    WinDev w;
+    rc = stage_window(c, j, not_before, deadline, w);
+    if (rc) return rc;
+    const size_t nn = (size_t)j * kmax;
+    if (c->out.ensure(nn) || c->outs.ensure(j)) return FIT_E_OOM;
+    rc = place_tl_k_impl(c, j, d, kmax, c->out.p, c->outs.p, stats, &w);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out_node, c->out.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipMemcpyAsync(out_start, c->outs.p, sizeof(int32_t) * j, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+int fit_place_tl_k_win_device(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,
+                              const int32_t* wall, const uint16_t* part, const uint16_t* nk, int32_t kmax,
+                              const int32_t* not_before, const int32_t* deadline, int32_t* out_node,
+                              int32_t* out_start, fit_stats* stats) {
+    const int rc =
+        check_tl_rows_args(c, j, {cpu, mem, gpu, wall, part, out_node, out_start}, kmax, "fit_place_tl_k_win");
+    if (rc) return rc;
+    if (j == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const WinDev w{not_before, deadline};
+    return place_tl_k_impl(c, j, {cpu, mem, gpu, wall, part, nk}, kmax, out_node, out_start, stats, &w);
 }
 
 int fit_unplace_tl(fit_ctx* c, int32_t j, const int32_t* cpu, const int32_t* mem, const int32_t* gpu,

@@ -209,6 +209,7 @@ enum EtaCode : int32_t {
     ETA_NO_NODES = 5,
     ETA_LATER = 6,
     ETA_HORIZON = 7,
+    ETA_WINDOW = 8,  // fit_when_k_win only: no start inside the job's window (SPEC §2r)
 };
 hipError_t launch_when_classify(hipStream_t st, const int32_t* ptab, int32_t np, const int32_t* jcpu,
                                 const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
@@ -235,6 +236,14 @@ hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab,
                               const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
                               int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
                               int32_t* diff, unsigned long long* top, void* out, int32_t* out_node);
+// fit_when_k_win: the chunk with the windowed count, pick and final.  nb / dl:
+// the job columns not_before and deadline on the device, either nullptr (all 0 / none).
+hipError_t launch_whenk_chunk_win(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                                  int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                                  const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
+                                  int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live,
+                                  int slices, int32_t* diff, unsigned long long* top, void* out, int32_t* out_node,
+                                  const int32_t* nb, const int32_t* dl);
 
 // ---- fit_place_tl_k (fit_place_tl_k.hip) -------------------------------
 // One workgroup per component walks its jobs in order; a launch takes at most PTLK_CHUNK jobs of
@@ -252,6 +261,12 @@ hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab
                               const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                               const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
                               int32_t* out_start, int32_t* placed);
+// fit_place_tl_k_win: the windowed commit, nb / dl as launch_whenk_chunk_win's
+hipError_t launch_ptlk_commit_win(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+                                  int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
+                                  const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                  const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
+                                  int32_t* out_start, int32_t* placed, const int32_t* nb, const int32_t* dl);
 
 // ---- the rows of fit_unplace_tl and fit_hold_tl, grouped by node (fit_unplace_tl.hip, DESIGN.md
 // §2h / §3.16) -----------------------------------------------------------------------------------

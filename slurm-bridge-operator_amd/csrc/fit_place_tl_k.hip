@@ -20,6 +20,8 @@
 //                     workgroup's smallest; (reserve) one wave per pick reserves with tl_reserve_any and refreshes the
 //                     node's header (tl_refresh_head).
 // The run-list pieces named in brackets are fit_tl_walk.h's, shared with fit_when_k.hip.
+// k_ptlk_commit is template <bool WIN>: WIN = true is fit_place_tl_k_win, the
+// same kernel over each job's allowed starts [from, until - d] only; WIN = false is the code above.
 // A component's rows are read and written by its workgroup alone, so nothing here waits for another
 // workgroup: no persistent grid, no launch lock, no watchdog.  Between jobs the waves of the
 // workgroup hand the run lists on through __syncthreads(), i.e. a workgroup-scope release before and
@@ -68,12 +70,19 @@ __host__ __device__ inline size_t ptlk_scr_bytes(int threads, int32_t H) {
 
 // grid = components; jl: the component-ordered job list, jb[c] .. jb[c + 1] component c's range of
 // it; this launch takes positions [t0, t0 + chunk) of every component's range.
+// WIN (fit_place_tl_k_win, SPEC §2r / DESIGN.md §3.27): a job's starts are A = [from, until - d].
+// The count clips every stretch as k_whenk_count<true> does; a run that ends at or before `from` is
+// stepped as infeasible, so the stretch minima begin at the first run that meets max(a, from) and
+// the "first window" a thread scores is the node's first ALLOWED window [ra, ra + d), ra + d <=
+// until.  The array holds allowed starts only, hence tl_first_start_in's `early` is "some node has
+// an allowed start in [from, start)", which is what the shortcut needs.
+template <bool WIN>
 __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
     TlHdr* hdr, Seg* slab, ExplainComps C, int32_t H, int32_t slot_min, const int32_t* __restrict__ jl,
     const int32_t* __restrict__ jb, int32_t t0, int32_t chunk, const int32_t* __restrict__ jcpu,
     const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu, const int32_t* __restrict__ jwall,
     const uint16_t* __restrict__ jpart, const uint16_t* __restrict__ jk, int32_t kmax, int32_t* out_node,
-    int32_t* out_start, int32_t* __restrict__ placed_total) {
+    int32_t* out_start, int32_t* __restrict__ placed_total, WinCols<WIN> win) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int c = blockIdx.x;
     if (c >= C.ncomp) return;
@@ -95,7 +104,14 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
         const int32_t need = tl_need(jk, q, kmax);
         const int32_t d = tl_dur(jwall[q], slot_min);  // fit_when_k's `dur`
         const uint32_t pbit = 1u << (jpart[q] & 31);
-        if (d > H) continue;  // no window inside the horizon: unplaced, nothing touched
+        int32_t from = 0, until = H;
+        if constexpr (WIN) {
+            from = tl_win_from(win, q, H);
+            until = tl_win_until(win, q, H);
+            if (from + d > until) continue;  // no allowed start: unplaced, nothing touched
+        } else {
+            if (d > H) continue;  // no window inside the horizon: unplaced, nothing touched
+        }
         // the last job's readers of pick[] are behind its closing barrier; two barriers lie between
         // this reset and the first minimum
         if (tid < FIT_KMAX) pick[tid] = KEY_INF;
@@ -116,22 +132,28 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
             int32_t mc = 0, mm = 0, mg = 0;         // minima of the current stretch's runs so far
             int32_t ks = -1, kc = 0, km = 0, kg = 0;  // the first window: its start and minima, frozen
             auto step = [&](const Seg& r, bool vr = true) {  // vr false: behind the last run
-                const bool f = vr & (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
+                bool f = vr & (r.cpu >= cpu) & (r.mem >= mem) & (r.gpu >= gpu);
+                if constexpr (WIN) f &= r.end > from;
                 if (!f && ra >= 0) {
-                    if (s0 - ra >= d) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
+                    int32_t b = s0;
+                    if constexpr (WIN) b = min(s0, until);
+                    if (b - ra >= d) {  // starts ra .. b - d: +1 at ra, -1 at b - d + 1 <= H
                         atomicAdd(&diff[ra], 1);
-                        atomicAdd(&diff[s0 - d + 1], -1);
+                        atomicAdd(&diff[b - d + 1], -1);
                     }
                     ra = -1;
                 }
                 const int32_t e1 = min(max(r.end, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
                 if (f && s0 < H) {
                     const bool nw = ra < 0;
-                    ra = nw ? s0 : ra;
+                    if constexpr (WIN) ra = nw ? max(s0, from) : ra;  // < e1: the run ends behind `from`
+                    else ra = nw ? s0 : ra;
                     mc = nw ? r.cpu : min(mc, r.cpu);
                     mm = nw ? r.mem : min(mm, r.mem);
                     mg = nw ? r.gpu : min(mg, r.gpu);
-                    if (ks < 0 && e1 - ra >= d) {  // the run that holds slot ra + d - 1 closes the first window
+                    bool first = ks < 0 && e1 - ra >= d;  // the run that holds slot ra + d - 1 closes the first window
+                    if constexpr (WIN) first = first && ra + d <= until;
+                    if (first) {
                         ks = ra;
                         kc = mc;
                         km = mm;
@@ -149,7 +171,9 @@ __global__ __launch_bounds__(PTLK_THREADS) void k_ptlk_commit(
 
         // ---- pick: the first start with `need` nodes free together
         if (wave == 0) {
-            const TlStart f = tl_first_start(diff, H, need, lane);
+            TlStart f;
+            if constexpr (WIN) f = tl_first_start_in(diff, from, until - d, need, lane);
+            else f = tl_first_start(diff, H, need, lane);
             if (lane == 0) {
                 sh[0] = f.start;
                 sh[1] = f.early;  // some node is free before the start: its first window is not the job's
@@ -250,19 +274,40 @@ size_t ptlk_lds_bytes(int threads, int32_t H) {
 }
 
 // Positions [t0, t0 + chunk) of every component's job list, in order, on stream st.
-hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+template <bool WIN>
+static hipError_t ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
                               int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
                               const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
                               const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
-                              int32_t* out_start, int32_t* placed) {
+                              int32_t* out_start, int32_t* placed, WinCols<WIN> win) {
     if (C.ncomp < 1 || C.ncomp > 32 || threads < 64 || threads > PTLK_THREADS || threads % 64 || H < 1 ||
         H > TL_MAX_SLOTS || slot_min < 1 || kmax < 1 || kmax > FIT_KMAX || t0 < 0 || chunk < 1 || chunk > PTLK_CHUNK)
         return hipErrorInvalidValue;
     const size_t lds = ptlk_lds_bytes(threads, H);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ptlk_commit, dim3(C.ncomp), dim3(threads), lds, st, hdr, slab, C, H, slot_min, jl, jb, t0,
-                       chunk, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, out_node, out_start, placed);
+    hipLaunchKernelGGL((k_ptlk_commit<WIN>), dim3(C.ncomp), dim3(threads), lds, st, hdr, slab, C, H, slot_min, jl, jb,
+                       t0, chunk, jcpu, jmem, jgpu, jwall, jpart, jk, kmax, out_node, out_start, placed, win);
     return hipGetLastError();
+}
+
+hipError_t launch_ptlk_commit(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
+                              const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                              const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
+                              int32_t* out_start, int32_t* placed) {
+    return ptlk_commit<false>(st, threads, hdr, slab, C, H, slot_min, jl, jb, t0, chunk, jcpu, jmem, jgpu, jwall, jpart,
+                              jk, kmax, out_node, out_start, placed, WinCols<false>{});
+}
+
+// fit_place_tl_k_win: the windowed commit; nb / dl: the job columns not_before and deadline on the
+// device, either nullptr (all 0 / none).
+hipError_t launch_ptlk_commit_win(hipStream_t st, int threads, TlHdr* hdr, Seg* slab, const ExplainComps& C, int32_t H,
+                                  int32_t slot_min, const int32_t* jl, const int32_t* jb, int32_t t0, int32_t chunk,
+                                  const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu, const int32_t* jwall,
+                                  const uint16_t* jpart, const uint16_t* jk, int32_t kmax, int32_t* out_node,
+                                  int32_t* out_start, int32_t* placed, const int32_t* nb, const int32_t* dl) {
+    return ptlk_commit<true>(st, threads, hdr, slab, C, H, slot_min, jl, jb, t0, chunk, jcpu, jmem, jgpu, jwall, jpart,
+                             jk, kmax, out_node, out_start, placed, WinCols<true>{nb, dl});
 }
 
 }  // namespace fitgpu

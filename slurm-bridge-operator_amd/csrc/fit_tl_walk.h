@@ -6,6 +6,8 @@
 //       (fit_when_k.hip, fit_place_tl_k.hip) share: the visit of every run, header then slab; the
 //       one window [start, stop); a lane's sorted key list; the first common start from a
 //       difference array
+//   WinCols, tl_win_from / tl_win_until, tl_first_start_in : the per-job window of allowed starts of
+//       the windowed instantiations (fit_when_k_win, fit_place_tl_k_win; SPEC §2r)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -173,6 +175,60 @@ __device__ __forceinline__ TlStart tl_first_start(const int32_t* diff, int32_t H
         v += carry;  // cnt(s)
         const uint64_t hit = __ballot(s < H && v >= need);
         const uint64_t some = __ballot(s < H && v > 0);
+        if (hit) {
+            const int first = __builtin_ctzll(hit);
+            r.start = base + first;
+            r.ready = __shfl(v, first);
+            r.early |= (some & ((1ull << first) - 1ull)) != 0;
+            break;
+        }
+        r.early |= some != 0;
+        carry = __shfl(v, 63);
+    }
+    return r;
+}
+
+// ---- the window of allowed starts (SPEC §2r) ---------------------------------------------------
+
+// The two optional job columns of the windowed entry points, as a kernel's last argument.  The
+// unwindowed instantiation carries the empty struct and reads nothing of it.
+template <bool WIN>
+struct WinCols {};
+template <>
+struct WinCols<true> {
+    const int32_t* nb;  // not_before per job; nullptr: all 0
+    const int32_t* dl;  // deadline per job; nullptr: none
+};
+__device__ __forceinline__ int32_t tl_win_from(const WinCols<false>&, int, int32_t) { return 0; }
+__device__ __forceinline__ int32_t tl_win_until(const WinCols<false>&, int, int32_t H) { return H; }
+// from = clamp(not_before, 0, H), until = clamp(deadline, 0, H): no value is an error
+__device__ __forceinline__ int32_t tl_win_from(const WinCols<true>& w, int q, int32_t H) {
+    return w.nb ? min(max(w.nb[q], 0), H) : 0;
+}
+__device__ __forceinline__ int32_t tl_win_until(const WinCols<true>& w, int q, int32_t H) {
+    return w.dl ? min(max(w.dl[q], 0), H) : H;
+}
+
+// tl_first_start over the allowed starts [from, last] only (last = until - d; the caller has
+// from <= last < H).  The count walks clip every stretch to the window, so the words before `from`
+// are zero and the words behind `last` take only -1s: the prefix sum may begin, with no carry, at
+// the 64-slot block that holds `from`, and cnt(from) is the word at `from` itself.  now: cnt(from);
+// early: some s in [from, start) has cnt(s) > 0.
+__device__ __forceinline__ TlStart tl_first_start_in(const int32_t* diff, int32_t from, int32_t last, int32_t need,
+                                                     int lane) {
+    TlStart r{-1, 0, diff[from], false};
+    int32_t carry = 0;
+    for (int base = from & ~63; base <= last; base += 64) {
+        const int s = base + lane;
+        int32_t v = s <= last ? diff[s] : 0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t u = __shfl_up(v, off);
+            if (lane >= off) v += u;
+        }
+        v += carry;  // cnt(s)
+        const uint64_t hit = __ballot(s <= last && v >= need);
+        const uint64_t some = __ballot(s <= last && v > 0);
         if (hit) {
             const int first = __builtin_ctzll(hit);
             r.start = base + first;

@@ -26,6 +26,8 @@
 //   k_whenk_final    : one wave per job: the `need` smallest of the slices' keys -> out_node
 //                      (TlHdr::orig, key order), wait_min and the code.
 // The run-list pieces named in brackets are fit_tl_walk.h's, shared with fit_place_tl_k.hip.
+// count, pick and final are template <bool WIN>: WIN = true is fit_when_k_win,
+// the same kernels over each job's allowed starts [from, until - d] only; WIN = false is the code above.
 // Cross-workgroup traffic is integer atomicAdd (commutative) or disjoint stores, so rows are exact
 // and reproducible.  No cross-workgroup wait of any kind: no watchdog, no persistent-launch lock.
 #include <hip/hip_runtime.h>
@@ -82,17 +84,24 @@ __global__ __launch_bounds__(256) void k_whenk_classify(
 // stretch state is one register per job.  With the jobs in component order a group is one
 // component but for a seam; a group passes once over each distinct component of its jobs, each job
 // judging only its own.
+// WIN (fit_when_k_win, SPEC §2r / DESIGN.md §3.27): a job counts only its allowed starts
+// A = [from, until - d].  A run that ends at or before `from` holds none and is stepped as infeasible,
+// so a stretch begins at max(a, from) at the earliest, and a closing stretch [a, b) is cut to
+// min(b, until): +1 at max(a, from), -1 at min(b, until) - d + 1, when that range is not empty.  The
+// words of a job's array before `from` stay zero.  A job whose A is empty walks nothing.
+template <bool WIN>
 __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
     const TlHdr* __restrict__ hdr, const Seg* __restrict__ slab, ExplainComps C, int32_t H, int32_t slot_min,
     int32_t t0, int32_t nj, const int32_t* __restrict__ jl, const int32_t* __restrict__ live, int32_t njobs,
     const int32_t* __restrict__ jcpu, const int32_t* __restrict__ jmem, const int32_t* __restrict__ jgpu,
     const int32_t* __restrict__ jwall, const uint16_t* __restrict__ jpart, const int8_t* __restrict__ jcomp,
-    EtaKRow* __restrict__ out, int32_t* __restrict__ diff) {
+    EtaKRow* __restrict__ out, int32_t* __restrict__ diff, WinCols<WIN> win) {
     __shared__ int32_t ld[WK_GROUP][TL_MAX_SLOTS + 1];
     __shared__ int32_t cnt[WK_GROUP][2];  // members, hosts
     const int tb = blockIdx.x * WK_GROUP;  // chunk-local position of the group's first job
     int32_t q[WK_GROUP], comp[WK_GROUP], cpu[WK_GROUP], mem[WK_GROUP], gpu[WK_GROUP], d[WK_GROUP];
     uint32_t pbit[WK_GROUP];
+    int32_t fr[WK_GROUP], un[WK_GROUP];  // WIN: the job's window; unused otherwise
     uint32_t valid = 0;
 #pragma unroll
     for (int g = 0; g < WK_GROUP; ++g) {
@@ -107,6 +116,10 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
         gpu[g] = on ? jgpu[qq] : 0;
         d[g] = on ? tl_dur(jwall[qq], slot_min) : 1;  // k_whenk_classify's `dur`
         pbit[g] = on ? 1u << (jpart[qq] & 31) : 0u;
+        if constexpr (WIN) {
+            fr[g] = on ? tl_win_from(win, qq, H) : 0;
+            un[g] = on ? tl_win_until(win, qq, H) : 0;
+        }
         valid |= on ? 1u << g : 0u;
     }
     if (!valid) return;  // block-uniform
@@ -137,7 +150,8 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
             for (int g = 0; g < WK_GROUP; ++g) {
                 const bool mb = ((act >> g) & 1u) && (h.mask & pbit[g]);
                 members[g] += mb;
-                lv |= mb && d[g] <= H && cpu[g] <= h.cpu && mem[g] <= h.mem && gpu[g] <= h.gpu ? 1u << g : 0u;
+                // WIN: some start is allowed at all
+                lv |= mb && (WIN ? fr[g] + d[g] <= un[g] : d[g] <= H) && cpu[g] <= h.cpu && mem[g] <= h.mem && gpu[g] <= h.gpu ? 1u << g : 0u;
             }
             if (!lv) continue;
             const Seg* sg = slab + (int64_t)x * TL_MAX_SLOTS;
@@ -152,16 +166,19 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
             auto step = [&](const Seg& r, bool vr = true) {
 #pragma unroll
                 for (int g = 0; g < WK_GROUP; ++g) {
-                    const bool f = vr & (bool)((lv >> g) & 1u) & (r.cpu >= cpu[g]) & (r.mem >= mem[g]) & (r.gpu >= gpu[g]);
+                    const bool f = vr & (bool)((lv >> g) & 1u) & (r.cpu >= cpu[g]) & (r.mem >= mem[g]) & (r.gpu >= gpu[g]) &
+                                   (WIN ? r.end > fr[g] : true);
                     if (!f && ra[g] >= 0) {
-                        if (s0 - ra[g] >= d[g]) {  // starts ra .. s0 - d: +1 at ra, -1 at s0 - d + 1 <= H
+                        const int32_t b = WIN ? min(s0, un[g]) : s0;
+                        if (b - ra[g] >= d[g]) {  // starts ra .. b - d: +1 at ra, -1 at b - d + 1 <= H
                             atomicAdd(&ld[g][ra[g]], 1);
-                            atomicAdd(&ld[g][s0 - d[g] + 1], -1);
+                            atomicAdd(&ld[g][b - d[g] + 1], -1);
                             any |= 1u << g;
                         }
                         ra[g] = -1;
                     }
-                    if (f && ra[g] < 0 && s0 < H) ra[g] = s0;
+                    // WIN: max(s0, from) < the run's end, which lies behind `from`
+                    if (f && ra[g] < 0 && s0 < H) ra[g] = WIN ? max(s0, fr[g]) : s0;
                 }
                 s0 = min(max(r.end, s0), H);  // canonical lists only grow; held so that 0 <= ra < s0 <= H whatever is read
             };
@@ -190,11 +207,15 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_count(
     }
 }
 
-// One wave per job, 4 jobs per workgroup: cnt(s) is the prefix sum of the differences.
+// One wave per job, 4 jobs per workgroup: cnt(s) is the prefix sum of the differences.  WIN: over
+// the allowed starts only (tl_first_start_in), `now` being cnt(from); an empty A leaves the row as
+// d > H does.
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_whenk_pick(const int32_t* __restrict__ diff, int32_t H, int32_t t0,
                                                     int32_t nj, const int32_t* __restrict__ jl,
                                                     const int32_t* __restrict__ live, int32_t njobs,
-                                                    const int8_t* __restrict__ jcomp, EtaKRow* __restrict__ out) {
+                                                    const int8_t* __restrict__ jcomp, EtaKRow* __restrict__ out,
+                                                    WinCols<WIN> win) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + wave;
@@ -202,8 +223,15 @@ __global__ __launch_bounds__(256) void k_whenk_pick(const int32_t* __restrict__ 
     const int q = query_job(t0 + t, jl, live, njobs);
     if (q < 0 || jcomp[q] < 0) return;  // rejected, or no member at all: start stays -1
     const int32_t need = out[q].need, d = out[q].dur;
-    if (d > H) return;
-    const TlStart f = tl_first_start(diff + (int64_t)t * (H + 1), H, need, lane);
+    TlStart f;
+    if constexpr (WIN) {
+        const int32_t from = tl_win_from(win, q, H), last = tl_win_until(win, q, H) - d;
+        if (from > last) return;
+        f = tl_first_start_in(diff + (int64_t)t * (H + 1), from, last, need, lane);
+    } else {
+        if (d > H) return;
+        f = tl_first_start(diff + (int64_t)t * (H + 1), H, need, lane);
+    }
     if (lane == 0) {
         out[q].now = f.now;
         out[q].start = f.start;
@@ -262,13 +290,15 @@ __global__ __launch_bounds__(WK_THREADS) void k_whenk_nodes(
 }
 
 // One wave per position, 4 per workgroup: the wave holds the slices' keys, two per lane, and takes
-// the `need` smallest in `need` rounds of a wave minimum; lane 0 writes the row.
+// the `need` smallest in `need` rounds of a wave minimum; lane 0 writes the row.  WIN: a job without
+// a start whose window is not the whole range ends as ETA_WINDOW.
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_whenk_final(EtaKRow* __restrict__ out, int32_t t0, int32_t nj,
                                                      const int32_t* __restrict__ jl,
                                                      const int32_t* __restrict__ live, int32_t njobs,
                                                      const unsigned long long* __restrict__ top, int slices,
                                                      const TlHdr* __restrict__ hdr, int32_t slot_min, int32_t kmax,
-                                                     int32_t* __restrict__ out_node) {
+                                                     int32_t* __restrict__ out_node, int32_t H, WinCols<WIN> win) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + wave;
@@ -281,6 +311,8 @@ __global__ __launch_bounds__(256) void k_whenk_final(EtaKRow* __restrict__ out, 
         r.code = ETA_NO_NODES;
     } else if (r.start < 0) {
         r.code = ETA_HORIZON;
+        if constexpr (WIN)
+            if (tl_win_from(win, q, H) != 0 || tl_win_until(win, q, H) != H) r.code = ETA_WINDOW;
         r.ready = 0;
     } else {
         r.wait_min = (int32_t)min<int64_t>((int64_t)r.start * slot_min, 0x7fffffff);
@@ -322,11 +354,13 @@ hipError_t launch_whenk_classify(hipStream_t st, const int32_t* ptab, int32_t np
 // finalise.  jl / live: the component-ordered job list and its length on the device (njobs jobs in
 // all), or nullptr for the caller's order.  diff: nj * (H + 1) words and top: nj * slices *
 // WHENK_KEYS keys of scratch, reused by the next chunk on the same stream.
-hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+template <bool WIN>
+static hipError_t whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
                               int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
                               const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
                               int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
-                              int32_t* diff, unsigned long long* top, void* out, int32_t* out_node) {
+                              int32_t* diff, unsigned long long* top, void* out, int32_t* out_node,
+                              WinCols<WIN> win) {
     if (nj <= 0) return hipSuccess;
     if (C.ncomp < 1 || C.ncomp > 32 || slices < 1 || slices > WHENK_MAX_SLICES || nj > WHENK_CHUNK || H < 1 ||
         H > TL_MAX_SLOTS || slot_min < 1 || kmax < 1 || kmax > FIT_KMAX || t0 < 0 || t0 + nj > njobs)
@@ -336,14 +370,36 @@ hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab,
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(top, 0xff, sizeof(unsigned long long) * (size_t)nj * slices * WHENK_KEYS, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_whenk_count, dim3((nj + WK_GROUP - 1) / WK_GROUP, slices), dim3(WK_THREADS), 0, st, hdr, slab,
-                       C, H, slot_min, t0, nj, jl, live, njobs, jcpu, jmem, jgpu, jwall, jpart, jcomp, o, diff);
-    hipLaunchKernelGGL(k_whenk_pick, dim3((nj + 3) / 4), dim3(256), 0, st, diff, H, t0, nj, jl, live, njobs, jcomp, o);
+    hipLaunchKernelGGL((k_whenk_count<WIN>), dim3((nj + WK_GROUP - 1) / WK_GROUP, slices), dim3(WK_THREADS), 0, st, hdr, slab,
+                       C, H, slot_min, t0, nj, jl, live, njobs, jcpu, jmem, jgpu, jwall, jpart, jcomp, o, diff, win);
+    hipLaunchKernelGGL((k_whenk_pick<WIN>), dim3((nj + 3) / 4), dim3(256), 0, st, diff, H, t0, nj, jl, live, njobs, jcomp,
+                       o, win);
     hipLaunchKernelGGL(k_whenk_nodes, dim3(nj, slices), dim3(WK_THREADS), 0, st, hdr, slab, C, H, t0, jl, live, njobs,
                        jcpu, jmem, jgpu, jpart, jcomp, o, top);
-    hipLaunchKernelGGL(k_whenk_final, dim3((nj + 3) / 4), dim3(256), 0, st, o, t0, nj, jl, live, njobs, top, slices,
-                       hdr, slot_min, kmax, out_node);
+    hipLaunchKernelGGL((k_whenk_final<WIN>), dim3((nj + 3) / 4), dim3(256), 0, st, o, t0, nj, jl, live, njobs, top,
+                       slices, hdr, slot_min, kmax, out_node, H, win);
     return hipGetLastError();
+}
+
+hipError_t launch_whenk_chunk(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                              int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                              const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
+                              int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live, int slices,
+                              int32_t* diff, unsigned long long* top, void* out, int32_t* out_node) {
+    return whenk_chunk<false>(st, hdr, slab, C, H, slot_min, jcpu, jmem, jgpu, jwall, jpart, t0, nj, njobs, kmax, jcomp,
+                              jl, live, slices, diff, top, out, out_node, WinCols<false>{});
+}
+
+// fit_when_k_win: the same sequence with the windowed count, pick and final; nb / dl: the job columns
+// not_before and deadline on the device, either nullptr (all 0 / none).
+hipError_t launch_whenk_chunk_win(hipStream_t st, const TlHdr* hdr, const Seg* slab, const ExplainComps& C, int32_t H,
+                                  int32_t slot_min, const int32_t* jcpu, const int32_t* jmem, const int32_t* jgpu,
+                                  const int32_t* jwall, const uint16_t* jpart, int32_t t0, int32_t nj, int32_t njobs,
+                                  int32_t kmax, const int8_t* jcomp, const int32_t* jl, const int32_t* live,
+                                  int slices, int32_t* diff, unsigned long long* top, void* out, int32_t* out_node,
+                                  const int32_t* nb, const int32_t* dl) {
+    return whenk_chunk<true>(st, hdr, slab, C, H, slot_min, jcpu, jmem, jgpu, jwall, jpart, t0, nj, njobs, kmax, jcomp,
+                             jl, live, slices, diff, top, out, out_node, WinCols<true>{nb, dl});
 }
 
 }  // namespace fitgpu

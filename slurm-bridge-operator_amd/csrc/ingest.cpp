@@ -1009,6 +1009,18 @@ int fit_when_k_message(const fit_eta_k* e, char* buf, int32_t buflen) {
     return (int)s.size();
 }
 
+// A fit_eta_k row of fit_when_k_win as one line: FIT_ETA_WINDOW's own text, every other code through
+// fit_when_k_message.  No device, no context.
+int fit_when_k_win_message(const fit_eta_k* e, char* buf, int32_t buflen) {
+    if (!e || !buf || buflen < 1) return FIT_E_INVAL;
+    if (e->code != FIT_ETA_WINDOW) return fit_when_k_message(e, buf, buflen);
+    const std::string s = "no start inside its window for " + std::to_string(e->need) + " nodes at once: " +
+                          std::to_string(e->hosts) + "/" + std::to_string(e->members) + " nodes can run it there";
+    if (s.size() + 1 > (size_t)buflen) return FIT_E_INVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return (int)s.size();
+}
+
 // A fit_room row as one line; the texts are fixed in include/fitgpu.h.  Codes 1-5 are fit_why's
 // with the same numbers and take its sentences.  No device, no context.
 int fit_room_message(const struct fit_room* r, char* buf, int32_t buflen) {

@@ -33,7 +33,7 @@ from ._lib import (FIT_E_PARSE, FIT_E_STATE, FIT_FLAG_COLLECTIVES, FIT_E_UNLIMIT
                    FitJobResources, FitNode, FitNodeTable, FitOpts, FitPodLabels, FitResources, FitStats, check, lib,
                    FIT_WHY_FITS, FIT_WHY_LIMIT_CPUS, FIT_WHY_LIMIT_MEM, FIT_WHY_LIMIT_TIME, FIT_WHY_NO_NODES,
                    FIT_WHY_PARTITION, FIT_WHY_RESOURCES, FitWhy,
-                   FIT_ETA_HORIZON, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
+                   FIT_ETA_HORIZON, FIT_ETA_WINDOW, FIT_ETA_LATER, FIT_ETA_LIMIT_CPUS, FIT_ETA_LIMIT_MEM, FIT_ETA_LIMIT_TIME,
                    FIT_ETA_NO_NODES, FIT_ETA_NOW, FIT_ETA_PARTITION, FitEta, FitEtaK, FIT_MAX_K,
                    FIT_ROOM_LIMIT_CPUS, FIT_ROOM_LIMIT_MEM, FIT_ROOM_LIMIT_TIME, FIT_ROOM_NO_NODES, FIT_ROOM_NONE,
                    FIT_ROOM_PARTITION, FIT_ROOM_SOME, FIT_ROOM_UNBOUNDED, FitRoom,
@@ -53,6 +53,7 @@ __all__ = [
     "FIT_WHY_LIMIT_CPUS", "FIT_WHY_LIMIT_MEM", "FIT_WHY_NO_NODES", "FIT_WHY_RESOURCES",
     "when_message", "ETA_DTYPE", "FIT_ETA_NOW", "FIT_ETA_PARTITION", "FIT_ETA_LIMIT_TIME", "FIT_ETA_LIMIT_CPUS",
     "FIT_ETA_LIMIT_MEM", "FIT_ETA_NO_NODES", "FIT_ETA_LATER", "FIT_ETA_HORIZON",
+    "FIT_ETA_WINDOW", "when_k_win_message",
     "when_k_message", "ETA_K_DTYPE", "FitEtaK", "FIT_MAX_K",
     "room_message", "ROOM_DTYPE", "FitRoom", "FIT_ROOM_SOME", "FIT_ROOM_PARTITION", "FIT_ROOM_LIMIT_TIME",
     "FIT_ROOM_LIMIT_CPUS", "FIT_ROOM_LIMIT_MEM", "FIT_ROOM_NO_NODES", "FIT_ROOM_NONE", "FIT_ROOM_UNBOUNDED",
@@ -389,6 +390,16 @@ def when_k_message(row) -> str:
     e = FitEtaK(*(int(get(n)) for n, _ in FitEtaK._fields_))
     buf = C.create_string_buffer(256)
     n = check(lib().fit_when_k_message(C.byref(e), buf, len(buf)), "fit_when_k_message")
+    return buf.raw[:n].decode()
+
+
+def when_k_win_message(row) -> str:
+    """A fit_eta_k row of when_k_win() as one line of text (fit_when_k_win_message): FIT_ETA_WINDOW's
+    own text, when_k_message's for every other code; needs no device."""
+    get = (lambda n: row[n]) if isinstance(row, (np.void, np.ndarray, dict)) else (lambda n: getattr(row, n))
+    e = FitEtaK(*(int(get(n)) for n, _ in FitEtaK._fields_))
+    buf = C.create_string_buffer(256)
+    n = check(lib().fit_when_k_win_message(C.byref(e), buf, len(buf)), "fit_when_k_win_message")
     return buf.raw[:n].decode()
 
 
@@ -735,6 +746,84 @@ class Engine:
         check(lib().fit_place_tl_k_device(self._h, int(cpu.numel()), _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
                                           _ptr(part), _ptr(nodes_k) if nodes_k is not None else None, int(kmax),
                                           _ptr(out_node), _ptr(out_start), C.byref(st)), "fit_place_tl_k_device")
+        return st.as_dict()
+
+    # ---- begin and deadline per job -----------------------------------------
+    @staticmethod
+    def _win_col(a, j, name):
+        """An optional window column from host memory: None, or J contiguous int32."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.int32)
+        if a.shape != (j,):
+            raise ValueError(f"{name} must have one entry per job")
+        return a
+
+    def when_k_win(self, jobs, not_before=None, deadline=None, kmax: int | None = None):
+        """when_k with a window of allowed starts per job (fit_when_k_win): not_before[J] and
+        deadline[J] in slots, either None (all 0 / none); a start s is allowed when
+        clamp(not_before, 0, H) <= s and s + dur <= clamp(deadline, 0, H).  Returns (rows, nodes) as
+        when_k; a job without a start inside a window that is not the whole range has code
+        FIT_ETA_WINDOW.  Changes nothing."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        j = len(part)
+        nb, dl = self._win_col(not_before, j, "not_before"), self._win_col(deadline, j, "deadline")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j else 1
+        out = np.zeros(j, ETA_K_DTYPE)
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        check(lib().fit_when_k_win(self._h, j, *[_ptr(c) for c in cols], _ptr(part), _ptr(k), int(kmax),
+                                   _ptr(nb) if nb is not None else None, _ptr(dl) if dl is not None else None,
+                                   _ptr(out), _ptr(nodes)), "fit_when_k_win")
+        return out, nodes
+
+    def when_k_win_device(self, cpu, mem, gpu, wall, part, nodes_k, not_before, deadline, out, out_node,
+                          kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k, not_before, deadline may each be
+        None); writes out and out_node as when_k_device.  Returns the device time of its launches in
+        ms (fit_when_k_win_ms); 0.0 for no jobs."""
+        j = int(cpu.numel())
+        opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
+        check(lib().fit_when_k_win_device(self._h, j, _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall), _ptr(part),
+                                          opt(nodes_k), int(kmax), opt(not_before), opt(deadline), _ptr(out),
+                                          _ptr(out_node)), "fit_when_k_win_device")
+        if j == 0:
+            return 0.0
+        ms = C.c_double()
+        check(lib().fit_when_k_win_ms(self._h, C.byref(ms)), "fit_when_k_win_ms")
+        return ms.value
+
+    def place_tl_k_win(self, jobs, not_before=None, deadline=None, kmax: int | None = None):
+        """place_tl_k with when_k_win's window per job (fit_place_tl_k_win): (nodes[J, kmax],
+        start[J], stats) as place_tl_k.  A job without an allowed start is unplaced and consumes
+        nothing."""
+        cols = [np.ascontiguousarray(a, np.int32) for a in (jobs.cpu, jobs.mem, jobs.gpu, jobs.wall)]
+        part = np.ascontiguousarray(jobs.part, np.uint16)
+        k = np.ascontiguousarray(jobs.nodes_k, np.uint16)
+        j = len(part)
+        nb, dl = self._win_col(not_before, j, "not_before"), self._win_col(deadline, j, "deadline")
+        if kmax is None:
+            kmax = max(1, int(k.max())) if j else 1
+        nodes = np.full((j, max(int(kmax), 0)), -1, np.int32)
+        start = np.full(j, -1, np.int32)
+        st = FitStats()
+        check(lib().fit_place_tl_k_win(self._h, j, *[_ptr(c) for c in cols], _ptr(part), _ptr(k), int(kmax),
+                                       _ptr(nb) if nb is not None else None, _ptr(dl) if dl is not None else None,
+                                       _ptr(nodes), _ptr(start), C.byref(st)), "fit_place_tl_k_win")
+        return nodes, start, st.as_dict()
+
+    def place_tl_k_win_device(self, cpu, mem, gpu, wall, part, nodes_k, not_before, deadline, out_node, out_start,
+                              kmax: int = 1):
+        """All arguments torch tensors resident on this GPU (nodes_k, not_before, deadline may each be
+        None); writes out_node (J * kmax int32) and out_start (J int32).  Returns the stats."""
+        st = FitStats()
+        opt = lambda t: _ptr(t) if t is not None else None  # noqa: E731
+        check(lib().fit_place_tl_k_win_device(self._h, int(cpu.numel()), _ptr(cpu), _ptr(mem), _ptr(gpu), _ptr(wall),
+                                              _ptr(part), opt(nodes_k), int(kmax), opt(not_before), opt(deadline),
+                                              _ptr(out_node), _ptr(out_start), C.byref(st)),
+              "fit_place_tl_k_win_device")
         return st.as_dict()
 
     # ---- hand reservations back to the timeline (DESIGN.md §2h) ----------------------------

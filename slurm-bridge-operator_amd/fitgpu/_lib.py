@@ -45,6 +45,8 @@ EXPORTS = [
     "fit_room", "fit_room_device", "fit_room_ms", "fit_room_message", "fit_admitter_room",
     "fit_when_k", "fit_when_k_device", "fit_when_k_ms", "fit_when_k_message",
     "fit_place_tl_k", "fit_place_tl_k_device",
+    "fit_when_k_win", "fit_when_k_win_device", "fit_when_k_win_ms", "fit_when_k_win_message",
+    "fit_place_tl_k_win", "fit_place_tl_k_win_device",
     "fit_unplace_tl", "fit_unplace_tl_device", "fit_unplace_tl_ms",
     "fit_advance_tl", "fit_advance_tl_device", "fit_advance_tl_ms",
     "fit_hold_tl", "fit_hold_tl_device", "fit_hold_tl_ms",
@@ -117,6 +119,7 @@ class FitWhy(C.Structure):
 # fit_eta.code (include/fitgpu.h): 1-5 are FIT_WHY_*'s; precedence 1, 2, 3, 4, 5, 7, 6, 0
 FIT_ETA_NOW, FIT_ETA_PARTITION, FIT_ETA_LIMIT_TIME, FIT_ETA_LIMIT_CPUS = 0, 1, 2, 3
 FIT_ETA_LIMIT_MEM, FIT_ETA_NO_NODES, FIT_ETA_LATER, FIT_ETA_HORIZON = 4, 5, 6, 7
+FIT_ETA_WINDOW = 8  # fit_when_k_win only: no start inside the job's window
 
 
 class FitEta(C.Structure):
@@ -231,6 +234,10 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, P]
         L.fit_when_k_ms.argtypes = [P, C.POINTER(C.c_double)]
         L.fit_when_k_message.argtypes = [C.POINTER(FitEtaK), C.c_char_p, i32]
+        for name in ("fit_when_k_win", "fit_when_k_win_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, P, P, P]
+        L.fit_when_k_win_ms.argtypes = [P, C.POINTER(C.c_double)]
+        L.fit_when_k_win_message.argtypes = [C.POINTER(FitEtaK), C.c_char_p, i32]
         for name in ("fit_room", "fit_room_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P]
         L.fit_room_ms.argtypes = [P, C.POINTER(C.c_double)]
@@ -268,6 +275,8 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, P, C.POINTER(FitStats)]
         for name in ("fit_place_tl_k", "fit_place_tl_k_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, P, C.POINTER(FitStats)]
+        for name in ("fit_place_tl_k_win", "fit_place_tl_k_win_device"):
+            getattr(L, name).argtypes = [P, i32, P, P, P, P, P, P, i32, P, P, P, P, C.POINTER(FitStats)]
         for name in ("fit_unplace_tl", "fit_unplace_tl_device"):
             getattr(L, name).argtypes = [P, i32, P, P, P, P, P, i32, P, P, C.POINTER(i64)]
         L.fit_unplace_tl_ms.argtypes = [P, C.POINTER(C.c_double)]

@@ -391,6 +391,58 @@ func (e *Engine) PlaceTLK(j Jobs, kmax int) (nodes, start []int32, st Stats, err
 	return nodes, start, st, check(rc)
 }
 
+// winCols gives the two optional window columns of PlaceTLKWin as C pointers: an empty
+// slice is NULL (notBefore: all 0, deadline: none), any other has one entry per job.
+func winCols(cnt int, notBefore, deadline []int32) (nb, dl *C.int32_t, err error) {
+	if (len(notBefore) != 0 && len(notBefore) != cnt) || (len(deadline) != 0 && len(deadline) != cnt) {
+		return nil, nil, errLen
+	}
+	if len(notBefore) > 0 {
+		nb = (*C.int32_t)(unsafe.Pointer(&notBefore[0]))
+	}
+	if len(deadline) > 0 {
+		dl = (*C.int32_t)(unsafe.Pointer(&deadline[0]))
+	}
+	return nb, dl, nil
+}
+
+// PlaceTLKWin is PlaceTLK with a window of allowed starts per job (DESIGN.md §2r): job q may start
+// at slot s only when clamp(notBefore[q], 0, H) <= s and s + d <= clamp(deadline[q], 0, H), d =
+// max(1, ceil(WallMin/slotMin)) — `sbatch --begin` / `--deadline` in slots, the planned end
+// start + d of a dependency's parent, the recorded start of a row HoldTL refused.  No value is an
+// error: a negative notBefore is 0, a deadline <= 0 has passed, math.MaxInt32 is none.  A job
+// without an allowed start is Unplaced and consumes nothing.  Empty notBefore / deadline: all 0 /
+// none; with both empty the result is PlaceTLK's.  Outputs and st as PlaceTLK.
+func (e *Engine) PlaceTLKWin(j Jobs, kmax int, notBefore, deadline []int32) (nodes, start []int32, st Stats, err error) {
+	cnt := len(j.CPU)
+	if kmax < 1 || kmax > MaxK {
+		return nil, nil, st, fmt.Errorf("fitgpu: kmax %d outside [1, %d]", kmax, MaxK)
+	}
+	if !sameLen(cnt, len(j.MemMiB), len(j.GPU), len(j.WallMin), len(j.Part)) ||
+		(len(j.NodesK) != 0 && len(j.NodesK) != cnt) {
+		return nil, nil, st, errLen
+	}
+	nb, dl, err := winCols(cnt, notBefore, deadline)
+	if err != nil {
+		return nil, nil, st, err
+	}
+	nodes, start = make([]int32, cnt*kmax), make([]int32, cnt)
+	if cnt == 0 {
+		return nodes, start, st, nil
+	}
+	var nk *C.uint16_t // NULL: every job takes one node
+	if len(j.NodesK) > 0 {
+		nk = (*C.uint16_t)(unsafe.Pointer(&j.NodesK[0]))
+	}
+	rc := C.fit_place_tl_k_win(e.ctx, C.int32_t(cnt), (*C.int32_t)(unsafe.Pointer(&j.CPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.MemMiB[0])), (*C.int32_t)(unsafe.Pointer(&j.GPU[0])),
+		(*C.int32_t)(unsafe.Pointer(&j.WallMin[0])), (*C.uint16_t)(unsafe.Pointer(&j.Part[0])),
+		nk, C.int32_t(kmax), nb, dl, (*C.int32_t)(unsafe.Pointer(&nodes[0])),
+		(*C.int32_t)(unsafe.Pointer(&start[0])), &st)
+	runtime.KeepAlive(e)
+	return nodes, start, st, check(rc)
+}
+
 // UnplaceTL hands reservations back to the loaded timeline (DESIGN.md §2h): row q adds its per-node
 // demand to slots [start[q], start[q]+d) of node[q*kmax .. +max(NodesK,1)), d = max(1,
 // ceil(WallMin/slotMin)).  j, node and start are the columns given to, and returned by, PlaceTLK
@@ -501,6 +553,7 @@ const (
 	EtaNoNodes   = int32(C.FIT_ETA_NO_NODES)
 	EtaLater     = int32(C.FIT_ETA_LATER)
 	EtaHorizon   = int32(C.FIT_ETA_HORIZON)
+	EtaWindow    = int32(C.FIT_ETA_WINDOW) // fit_when_k_win only: no start inside the job's window
 )
 
 // Eta is one fit_eta row: the job judged alone against the current timeline (DESIGN.md §2d).
