@@ -1,11 +1,13 @@
 // dev_decider_bench.hip — diagnostic only (never linked into the product): the decider loop of
 // fit_commit_mw.h alone on one wave, records pre-filled in LDS and no helper waves, to measure
-// its intrinsic cycles per job.  Built into fitgpu/libdecbench.so by `make decbench`.
+// its intrinsic cycles per job.  Built into fitgpu/libdecbench.so by `make decbench`
+// (-DDEC_SLIM: the slim ring of a one-partition component, mw_decide SP).
 #define MW_DECIDER_BENCH 1
 #include "fit_commit_mw.h"
 
 namespace fitgpu {
-__global__ __launch_bounds__(64) void k_dec_bench(int w, int32_t* out, unsigned long long* cyc) {
+__global__ __launch_bounds__(64) void k_dec_bench(int w, int32_t* out, unsigned long long* cyc,
+                                                      const NodeRec* rec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MwShared* S = reinterpret_cast<MwShared*>(smem);
     const int lane = threadIdx.x;
@@ -32,7 +34,11 @@ __global__ __launch_bounds__(64) void k_dec_bench(int w, int32_t* out, unsigned 
     P.ne = 2048;
     P.w = w;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+#ifdef DEC_SLIM
+    const CommitResult r = mw_decider<false, true>(P, S, out, 1, rec);
+#else
     const CommitResult r = mw_decider<false>(P, S, out, 1);
+#endif
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (lane == 0) {
         cyc[0] = t1 - t0;
@@ -48,8 +54,11 @@ extern "C" int dec_bench(int w, unsigned long long* host_out) {
     unsigned long long* cyc;
     if (hipMalloc(&out, sizeof(int32_t) * (w + 64)) != hipSuccess) return -1;
     if (hipMalloc(&cyc, 64) != hipSuccess) return -1;
+    fitgpu::NodeRec* rec;  // the node rows the slim ring's placement store reads ids from
+    if (hipMalloc(&rec, sizeof(fitgpu::NodeRec) * 2048) != hipSuccess) return -1;
+    if (hipMemset(rec, 0, sizeof(fitgpu::NodeRec) * 2048) != hipSuccess) return -1;
     const size_t lds = fitgpu::mw_lds_bytes(2048);
-    hipLaunchKernelGGL(fitgpu::k_dec_bench, dim3(1), dim3(64), lds, 0, w, out, cyc);
+    hipLaunchKernelGGL(fitgpu::k_dec_bench, dim3(1), dim3(64), lds, 0, w, out, cyc, rec);
     if (hipDeviceSynchronize() != hipSuccess) return -2;
     hipMemcpy(host_out, cyc, 32, hipMemcpyDeviceToHost);
 #ifdef MW_SEGSTAMP
@@ -57,5 +66,6 @@ extern "C" int dec_bench(int w, unsigned long long* host_out) {
 #endif
     hipFree(out);
     hipFree(cyc);
+    hipFree(rec);
     return 0;
 }

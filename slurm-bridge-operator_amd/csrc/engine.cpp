@@ -414,6 +414,7 @@ struct fit_ctx : CtxHandles {
     int32_t nn = 0;          // rows in components (mask != 0)
     int ncomp = 0;
     int comp_of_part[32];
+    bool comp_onepart[32] = {false};  // the component is exactly one partition (CompState::onepart)
     std::vector<int32_t> nb;  // ncomp + 1 component offsets (positions)
     DBuf<NodeRec> rec;
     DBuf<int32_t> col_cpu, col_mem, col_gpu, col_av, perm;
@@ -513,6 +514,7 @@ int load_nodes_common(fit_ctx* c, int32_t n) {
             c->cls_maxn = std::max(c->cls_maxn, nk);
             if (parts_of[k] != 1) c->cls_nodes_ok = false;
         }
+        for (int k = 0; k < 32; ++k) c->comp_onepart[k] = k < c->ncomp && parts_of[k] == 1;
         if (c->cls_maxn > class_max_nodes() || class_lds_bytes(c->cls_maxn) > 160 * 1024)
             c->cls_nodes_ok = false;
     }
@@ -671,6 +673,7 @@ int engine_plan(fit_ctx* c, const std::vector<int32_t>& jb, const EngineComps& E
         s.nb = s.sb = c->nb[k];
         s.ne = s.se = c->nb[k + 1];
         slice(s.ne - s.nb, s);
+        s.onepart = c->comp_onepart[k] ? 1 : 0;
         max_slices = std::max(max_slices, s.nslice);
         s.jstart = jb[k];
         s.jend = jb[k + 1];

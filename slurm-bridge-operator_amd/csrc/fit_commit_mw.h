@@ -154,7 +154,8 @@ struct alignas(16) MwShared {
     int32_t mind[3];   // the component's minimum cpu / mem / gpu demand over its non-rejected jobs
                        // (set by the committer at launch): a row below one of them is dead
     uint32_t ucap;     // dirty capacity of this component's commits: MW_UCAP (recycling) or UCAP
-    uint32_t pad1[1];
+    uint32_t slim;     // 1: the component is one partition (CompState::onepart, set by the committer
+                       // at launch): the decider runs the slim ring (mw_decide SP)
     MwRec rec[MW_R];
     MwRow rows[UCAP];  // ucap == MW_UCAP: rows[MW_UCAP ..) hold retired[] (mw_retired)
     uint32_t bitmap[1];  // (ne - nb + 31) / 32 words, dirty membership by position
@@ -709,9 +710,11 @@ struct MwDec {
     unsigned long long seg[8], prev;
 #endif
 };
-// diagnostic (decbench only): cycles per segment of a decider step, s_memtime at each point
+// diagnostic (never shipped): cycles per segment of a decider step, s_memtime at each point.  The
+// decider bench keeps its one launch's sums; in the engine (a -DMW_SEGSTAMP variant build) every
+// decider adds its sums and, in g_seg[8], its live jobs (fit_debug_mw_seg, tools/mw_seg.py).
 #ifdef MW_SEGSTAMP
-__device__ unsigned long long g_seg[8];
+__device__ unsigned long long g_seg[9];
 #define MW_SEG(D_, i)                                                                           \
     do {                                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                      \
@@ -807,6 +810,33 @@ __device__ __forceinline__ int mw_recycle(MwShared* S, const CompPlan& P, MwDec&
     return s;
 }
 
+// The slim ring's placement store (mw_decide SP): a group of up to 64 parked placements {job oq,
+// winner's position ov (-1: unplaced)} is translated to node ids by one load per lane, issued when
+// the group is complete and consumed when the NEXT group is complete (or at the decider's end), so
+// the decider's chain never waits for it.  pos lies in the component's [nb, ne): it comes from a
+// key of one of its nodes.
+#ifndef MW_POSOUT
+#define MW_POSOUT 1  // 0: the slim ring keeps the node id (the A/B arm of the position store)
+#endif
+struct MwPend {
+    int32_t q, id;  // per lane: job of the pending group (-1: none), its node id (loaded)
+};
+__device__ __forceinline__ void mw_store_pending(MwPend& pend, int32_t* out, int kmax) {
+    if (pend.q >= 0) ((GAS int32_t*)out)[(int64_t)pend.q * kmax] = pend.id;
+    pend.q = -1;
+}
+__device__ __forceinline__ void mw_store_group(MwPend& pend, int32_t oq, int32_t ov, int32_t* out,
+                                               int kmax, const GAS NodeRec* rec) {
+    // the group before: its ids were loaded 64 jobs ago.  Waited for here, on every path and
+    // before the store: left to the compiler, the wait lands behind the (exec-masked) store, where
+    // it waits for that store as well before pend.id may be rewritten.
+    __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+    mw_store_pending(pend, out, kmax);
+    pend.q = oq;
+    pend.id = -1;
+    if (oq >= 0 && ov >= 0) pend.id = rec[ov].orig;
+}
+
 // One job of the decider: job D.t with record `cur` (its data read after an acquire of the ready
 // word `flag`; refreshed in place on the slow path), `nxt` receives record t+1.  E = t & 7 is a
 // compile-time constant.  Straight-line: the decision is computed unconditionally and selected (no
@@ -815,13 +845,23 @@ __device__ __forceinline__ int mw_recycle(MwShared* S, const CompPlan& P, MwDec&
 // is set the step has no effect: the caller tests it once per 8 jobs.
 // RC: the 64-row set with recycling (MwShared::ucap == MW_UCAP); else UCAP rows and the
 // parent's code, instruction for instruction.
-template <int E, bool RC>
+// SP: the slim ring of a component that is exactly one partition (MwShared::slim).  Every node's
+// mask and every job's pbit is then that partition's bit, so the ring rows' partition test is
+// always true: the ring's mask lane is set to all ones once and never selected, read or written
+// again (rows[].mask holds all ones, which the helpers' unchanged tests pass).  The node id leaves
+// the ring as well: the winner's POSITION is parked as the placement and translated to its id
+// (rec[pos].orig, static: write-backs touch cpu, mem and gpu only) where 64 placements are stored
+// (mw_store_group).  rows[].orig and the items' orig / mask are then unused.  !SP: the code of
+// components of several partitions, unchanged.
+template <int E, bool RC, bool SP>
 __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec& D, MwRing& R,
                                           MwRecRegs& cur, MwRecRegs& nxt, uint32_t& flag,
                                           int32_t& oq, int32_t& ov, int32_t* out, int kmax,
-                                          uint64_t& waitcyc) {
+                                          uint64_t& waitcyc, MwPend& pend,
+                                          const GAS NodeRec* rec) {
     const int lane = threadIdx.x & 63;
     const int t = D.t;
+    constexpr bool PO = SP && MW_POSOUT;  // the node id off the ring
 #ifdef MW_DECIDER_BENCH
     if (t >= P.w) D.exit = true;  // pre-filled records: no end record
 #endif
@@ -862,8 +902,10 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         const uint32_t pv = *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)x.i2.y;
         // live ring rows at their current state
         const bool live = R.b.w >= v;
-        const uint64_t rk0 = fit_key(R.a.x, R.a.y, R.a.z, R.a.w, (uint32_t)R.b.x, (uint32_t)R.b.y,
-                                     jc, jm, jg, jw, jp);
+        const uint64_t rk0 = SP ? fit_key(R.a.x, R.a.y, R.a.z, R.a.w, ~0u, (uint32_t)R.b.y, jc, jm,
+                                          jg, jw, ~0u)  // one partition: no test
+                                : fit_key(R.a.x, R.a.y, R.a.z, R.a.w, (uint32_t)R.b.x, (uint32_t)R.b.y,
+                                          jc, jm, jg, jw, jp);
         const uint64_t rkey = live ? rk0 : KEY_INF;
         const uint32_t ip = x.i0.x;
         const bool stale = (pv & x.i2.z) >= x.i2.w;
@@ -876,8 +918,8 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
         d.sm = (tr ? R.a.y : (int32_t)x.i1.y) - jm;
         d.sg = (tr ? R.a.z : (int32_t)x.i1.z) - jg;
         d.sa = tr ? R.a.w : (int32_t)x.i1.w;
-        d.sk = tr ? R.b.x : (int32_t)x.i2.x;
-        d.so = tr ? R.b.z : (int32_t)x.i0.w;
+        d.sk = SP ? 0 : tr ? R.b.x : (int32_t)x.i2.x;
+        d.so = PO ? 0 : tr ? R.b.z : (int32_t)x.i0.w;
         d.ss = tr ? R.slot : (int32_t)x.i0.z;
         const uint64_t best = min8_2pass(cand);
         // lanes 0..7 all hold `best`; the winner is the lane whose candidate equals it
@@ -949,7 +991,8 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
     const int w = d.w;
     const int32_t pos = (int32_t)(uint32_t)d.bs;
     const int32_t nc = readlane(d.sc, w), nm = readlane(d.sm, w), ng = readlane(d.sg, w);
-    const int32_t na = readlane(d.sa, w), nk = readlane(d.sk, w), no = readlane(d.so, w);
+    const int32_t na = readlane(d.sa, w);
+    const int32_t nk = SP ? 0 : readlane(d.sk, w), no = PO ? pos : readlane(d.so, w);
     const int32_t slot = fresh ? D.nu : d.wslot;
     // an older ring entry of the same node dies (lane E is rewritten below)
     R.b.w = (placed && R.b.y == pos) ? -1 : R.b.w;
@@ -957,9 +1000,9 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
     R.a.y = writelane_c<E>(nm, R.a.y);
     R.a.z = writelane_c<E>(ng, R.a.z);
     R.a.w = writelane_c<E>(na, R.a.w);
-    R.b.x = writelane_c<E>(nk, R.b.x);
+    if constexpr (!SP) R.b.x = writelane_c<E>(nk, R.b.x);
     R.b.y = writelane_c<E>(pos, R.b.y);
-    R.b.z = writelane_c<E>(no, R.b.z);
+    if constexpr (!PO) R.b.z = writelane_c<E>(no, R.b.z);
     R.b.w = writelane_c<E>(placed ? t : -1, R.b.w);
     R.slot = writelane_c<E>(slot, R.slot);
     MW_SEG(D, 4);
@@ -1000,7 +1043,11 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
     oq = writelane(rfl((int32_t)cur.h0.w), t & 63, oq);
     ov = writelane(placed ? no : -1, t & 63, ov);
     if (E == 7 && go && (t & 63) == 63) {  // uniform, once per 64 jobs: store 64 placements
-        if (oq >= 0) ((GAS int32_t*)out)[(int64_t)oq * kmax] = ov;
+        if constexpr (PO) {
+            mw_store_group(pend, oq, ov, out, kmax, rec);
+        } else {
+            if (oq >= 0) ((GAS int32_t*)out)[(int64_t)oq * kmax] = ov;
+        }
         oq = -1;
     }
     D.t = t + (go ? 1 : 0);
@@ -1009,9 +1056,12 @@ __device__ __forceinline__ void mw_decide(MwShared* S, const CompPlan& P, MwDec&
 
 // Out of line (as is mw_helper): called once per round, each gets its own register allocation
 // instead of sharing the persistent kernel's (which otherwise spills SGPRs in this loop).
-template <bool RC>
+template <bool RC, bool SP = false>
 __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* Sin,
-                                                int32_t* __restrict__ out, int kmax) {
+                                                int32_t* __restrict__ out, int kmax,
+                                                const NodeRec* __restrict__ rec_ = nullptr) {
+    const GAS NodeRec* const rec = gview(rec_);  // SP: the placement store's id lookup
+    MwPend pend{-1, -1};
     const CompPlan P = plan_sgpr(Pref);  // by value (see mw_helper)
     MwShared* const S = lds_opaque(Sin);
     const int lane = threadIdx.x & 63;
@@ -1023,7 +1073,7 @@ __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* 
 #endif
     MwRing R;
     R.a = v4i32{0, 0, 0, 0};
-    R.b = v4i32{0, -1, -1, -1};  // dead, position matching no item
+    R.b = v4i32{SP ? -1 : 0, -1, -1, -1};  // dead, position matching no item (SP: mask all ones)
     R.slot = -1;
     int32_t oq = -1, ov = -1;  // placement of job t parked in lane t & 63, stored 64 at a time
     uint64_t waitcyc = 0;
@@ -1059,17 +1109,22 @@ __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* 
     // 8-way unrolled: the ring lane (t & 7) is a constant in every step; the two record register
     // sets alternate with the step's parity; the exit is tested once per 8 steps
     while (!D.exit) {
-        mw_decide<0, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<1, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<2, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<3, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<4, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<5, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<6, RC>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc);
-        mw_decide<7, RC>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc);
+        mw_decide<0, RC, SP>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<1, RC, SP>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<2, RC, SP>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<3, RC, SP>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<4, RC, SP>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<5, RC, SP>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<6, RC, SP>(S, P, D, R, ra, rb, flag, oq, ov, out, kmax, waitcyc, pend, rec);
+        mw_decide<7, RC, SP>(S, P, D, R, rb, ra, flag, oq, ov, out, kmax, waitcyc, pend, rec);
     }
     const int t = D.t;
-    if (oq >= 0 && lane < (t & 63)) ((GAS int32_t*)out)[(int64_t)oq * kmax] = ov;  // last group
+    if constexpr (SP && MW_POSOUT) {  // the pending group, then the last, partial one
+        mw_store_group(pend, lane < (t & 63) ? oq : -1, ov, out, kmax, rec);
+        mw_store_pending(pend, out, kmax);
+    } else {
+        if (oq >= 0 && lane < (t & 63)) ((GAS int32_t*)out)[(int64_t)oq * kmax] = ov;  // last group
+    }
     // final {decided, nu}, then halt (the helpers' exit)
     lds_release();
     __hip_atomic_store(&S->dn, ((uint64_t)(uint32_t)D.nu << 32) | (uint32_t)t, __ATOMIC_RELAXED,
@@ -1079,8 +1134,14 @@ __device__ __noinline__ CommitResult mw_decider(const CompPlan& Pref, MwShared* 
     MW_CLK(d1);
     MW_ADD(0, d1 - d0);
 #ifdef MW_SEGSTAMP
-    if (lane == 0)
+    if (lane == 0) {
+#ifdef MW_DECIDER_BENCH
         for (int i = 0; i < 8; ++i) g_seg[i] = D.seg[i];
+#else
+        for (int i = 0; i < 8; ++i) atomicAdd(&g_seg[i], D.seg[i]);
+        atomicAdd(&g_seg[8], (unsigned long long)t);
+#endif
+    }
 #endif
     MW_ADD(1, waitcyc);
     MW_ADD(2, t);
@@ -1112,8 +1173,12 @@ __device__ __forceinline__ CommitResult commit_window_mw(const CompPlan& P, MwSh
     __syncthreads();
     if (wave == 0) {
         // block-uniform: the 64-row set with recycling, or UCAP rows
-        const CommitResult r = S->ucap == (uint32_t)MW_UCAP ? mw_decider<true>(P, S, out, kmax)
-                                                            : mw_decider<false>(P, S, out, kmax);
+        // ... and the slim ring where the component is one partition
+        const bool rc = S->ucap == (uint32_t)MW_UCAP;
+        const CommitResult r = S->slim ? (rc ? mw_decider<true, true>(P, S, out, kmax, rec)
+                                             : mw_decider<false, true>(P, S, out, kmax, rec))
+                                       : (rc ? mw_decider<true>(P, S, out, kmax)
+                                             : mw_decider<false>(P, S, out, kmax));
         if (threadIdx.x == 0) put_result(S->res, r);
     } else {
         // waves 1.. : helpers 1..MW_H, with one or two dirty rows per lane (block-uniform)

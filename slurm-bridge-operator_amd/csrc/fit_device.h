@@ -82,7 +82,9 @@ struct CompState {
     int32_t slot0;         // fixed window slot region (even rounds)
     int32_t wmin, wmax;
     int32_t ks;            // keys per (job, block-slice) (CompPlan::ks)
-    int64_t cand_alt;      // the same for odd rounds (fit_engine_ctl.h: two buffer sets by parity)
+    int32_t onepart;       // 1: the component is exactly one partition — every node's mask and every
+                           // job's pbit is that partition's bit (k_engine's slim ring)
+    int64_t cand_alt;     // the same for odd rounds (fit_engine_ctl.h: two buffer sets by parity)
     int32_t slot_alt;
     int32_t pair_off;      // half-slice list scratch (even rounds; odd: + PAIR_AREA)
 };

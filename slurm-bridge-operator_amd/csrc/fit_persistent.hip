@@ -40,6 +40,9 @@ __device__ __noinline__ CommitResult engine_commit_single(int c, const CompPlan 
                                        (GAS int32_t*)out, kmax, (LdsWords)(uintptr_t)a, sa);
 }
 
+#ifndef MW_SLIM
+#define MW_SLIM 1  // 0: every component runs the full ring (the A/B arm of the slim ring)
+#endif
 #ifndef FIT_K0
 #define FIT_K0 4  // > 0: a round's first job tile keeps FIT_K0 keys per block-slice (scan_tile KW)
 #endif
@@ -98,6 +101,9 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_engine(
             // fewer keys per slice (its sub-slices would exceed the target: > 16k nodes) pays its
             // round starts dearly and keeps 128 rows (C3o: 837 rounds against 1,100)
             M->ucap = S.ks == KS ? (uint32_t)MW_UCAP : (uint32_t)UCAP;
+            // one partition: no partition test on the decider's ring, positions parked as
+            // placements (fit_commit_mw.h mw_decide SP)
+            M->slim = MW_SLIM && S.onepart != 0 ? 1u : 0u;
         }
         const Committer K{ctl, comp_ring(ring, c, ncomp), plans, bnd, c, wd};
         RoundAcct A;
@@ -286,6 +292,12 @@ hipError_t launch_engine(int blocks, size_t lds, hipStream_t st, void* ctl, void
 #ifdef FIT_TILE0_STAMPS
 extern "C" int fit_debug_tile0(unsigned long long* out /* 8 */) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(fitgpu::g_tile0), sizeof(fitgpu::g_tile0)) == hipSuccess ? 0 : -2;
+}
+#endif
+#ifdef MW_SEGSTAMP
+// the decider's per-segment cycle sums over the launches so far and, in [8], its live jobs
+extern "C" int fit_debug_mw_seg(unsigned long long* out /* 9 */) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(fitgpu::g_seg), sizeof(fitgpu::g_seg)) == hipSuccess ? 0 : -2;
 }
 #endif
 #ifdef FIT_STAMPS
